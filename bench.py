@@ -6,7 +6,7 @@ per GPU, bit widths 1..32 swept as 32 equal consecutive segments, 10%
 exceptions (bw <= 28; benchmarks/ab_test.cpp:1448, :1610-1631), synthetic data
 generated on the GPU.  The packed stream is produced by our GPU encoder
 (untimed; parity-tested against the reference-pinned oracle) and the timed
-decode is verified bit-exact at full size afterwards.  One step = one
+decode is verified bit-exact at full size afterwards (--full).  One step = one
 tpf_p4dec256v32_batch launch over the whole shard, inputs resident in HBM.
 
 Other workloads (--workload, one JSON line each, for DESIGN.md):
@@ -18,8 +18,8 @@ Other workloads (--workload, one JSON line each, for DESIGN.md):
   c4      p4Enc256v32 + p4Dec256v32 round trip (0/5/10/25% exceptions) and
           the 256v64 round trip (bw 1..64 with exceptions above bit 32)
   sweep   SURVEY §8(d): 10M blocks for EACH bit width 1..32, decode vs probe
---e2e adds the host-memory rates (pinned H2D + decode + D2H, tpf_host_dec; and
-      the encode trip, tpf_host_enc).
+--full --e2e adds the host-memory rates (pinned H2D + decode + D2H,
+      tpf_host_dec; and the encode trip, tpf_host_enc).
 
 Multi-GPU: `python bench.py --gpus N` (N > 1, WORLD_SIZE unset) starts
 `torch.distributed.run` with N ranks as a child process before anything
@@ -31,9 +31,25 @@ total, tpf_shard.chained_base).  --selftest runs the same launcher, process
 group and timing plumbing with a CPU stand-in step (gloo; no GPU, no codec)
 for the CPU tests.
 
-Rank 0 prints ONE JSON line with `roofline` (decode kernel, HIP events on
-the launch stream) and `cpu_baseline` (the reference library compiled from
-its own sources, run on this host's cores on a bounded sample).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs and no more: it generates and encodes the data, warms up, times
+the N steps and prints the line; `roofline` then holds what the timed steps'
+own HIP events give, and every figure that takes a run of its own is null.
+--full adds those runs: the full-size verification of the decode and its
+checksums, the data-movement probes, the HBM ceilings, the separately timed
+halves and the 64-bit leg of c4, the CPU baselines (`cpu_baseline`: the
+reference library compiled from its own sources, run on this host's cores on
+a bounded sample) and, with --e2e, the host-memory rates.  Without --full,
+`verified` is null and the exit status says nothing about correctness.
+
+--dump-outputs DIR writes what the timed path returned in its LAST timed step
+as DIR/<name>.npy (float64, every integer exact): a fixed, seeded sample of
+rows (`<name>.npy`, the sampled row numbers in `<name>_rows.npy`) and the
+sum of the whole array mod 2^64 as [low 32 bits, high 32 bits]
+(`<name>_sum.npy`).  The inputs depend on the arguments alone, so two builds
+run with the same arguments can be compared file for file.
+
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one timed step.
 """
 import argparse
 import ctypes
@@ -131,6 +147,59 @@ def checksum(t, dev, dist_on):
     if dist_on:
         torch.distributed.all_reduce(c)
     return int(c.item()) & ((1 << 64) - 1)
+
+
+# ------------------------------------------------------------ dump outputs
+DUMP_SEED = 20250117
+DUMP_VALUES = (48 << 20) // 8  # float64 values over all arrays of one dump: the files stay under 64 MB in all
+DUMP_CHUNK = 1 << 26
+
+
+def _unsigned_sum(flat):
+    """Sum of the elements of a flat uint8 / int32 tensor read as unsigned, mod 2^64 (chunked: no full-size temporary)."""
+    s = 0
+    for a in range(0, flat.numel(), DUMP_CHUNK):
+        c = flat[a:a + DUMP_CHUNK]
+        s += int(c.sum(dtype=torch.int64).item())
+        if flat.dtype == torch.int32:
+            s += int((c < 0).sum().item()) << 32
+    return s & ((1 << 64) - 1)
+
+
+def dump_outputs(args, rank, arrays):
+    """--dump-outputs DIR: `arrays` maps a name to a device tensor the timed
+    path returned in its last timed step (uint8 bytes, or 32- / 64-bit
+    integers as rows x width; a flat tensor is cut into rows of 256).  64-bit
+    elements are written as their two 32-bit words (low word first), 32-bit
+    ones as unsigned, so every float64 written is exact.  Per array:
+    NAME.npy (the rows drawn by default_rng(DUMP_SEED), ascending; the whole
+    array when it is small), NAME_rows.npy (their numbers) and NAME_sum.npy
+    (the unsigned sum of all its words mod 2^64 as [low 32 bits, high 32]).
+    Ranks above 0 write NAME_rank<r>."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_VALUES // len(arrays)
+    for name, t in arrays.items():
+        width = t.shape[-1] if t.dim() > 1 else 256
+        flat = t.reshape(-1)
+        if flat.element_size() == 8:
+            flat, width = flat.view(torch.int32), 2 * width
+        assert flat.dtype in (torch.uint8, torch.int32), flat.dtype
+        nrows = flat.numel() // width
+        if flat.numel() <= budget:
+            rows, sample = np.arange(nrows), flat
+        else:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nrows, min(nrows, budget // width), replace=False))
+            sample = flat[:nrows * width].view(nrows, width)[torch.from_numpy(rows).to(flat.device)]
+        sample = sample.to(torch.int64)
+        if flat.dtype == torch.int32:
+            sample &= 0xFFFFFFFF
+        total = _unsigned_sum(flat)
+        stem = os.path.join(args.dump_outputs, name if rank == 0 else f"{name}_rank{rank}")
+        np.save(stem + ".npy", sample.to(torch.float64).cpu().numpy())
+        np.save(stem + "_rows.npy", rows.astype(np.float64))
+        np.save(stem + "_sum.npy", np.array([total & 0xFFFFFFFF, total >> 32], dtype=np.float64))
 
 
 # --------------------------------------------------------- profile traffic
@@ -486,6 +555,16 @@ def per_rank_stats(world, dev, kernel_ms, achieved_GBps):
              "frac": round(gbs / HBM_PEAK_GBS, 4)} for r, (ms, gbs) in enumerate(rows)]
 
 
+def verdict(ok):
+    """The word the `data` field carries for a workload's `verified` (None: a run without --full checks nothing)."""
+    return "not checked in this run (--full checks)" if ok is None else ("ok" if ok else "MISMATCH")
+
+
+def no_cpu(args, world):
+    """CPU baselines run under --full only, at one GPU, unless --no-cpu-baseline."""
+    return not args.full or args.no_cpu_baseline or world > 1
+
+
 def line(metric, value, unit, world, steps, warmup, elapsed, dtype, data, config, roofline=None, cpu=None):
     return {
         "metric": metric,
@@ -526,19 +605,20 @@ def run_c2(args, world, rank, dev, T, c5=False):
     out = torch.empty((nb, 256), dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int64, device=dev)
     elapsed, kern_ms = T.run(lambda: tpf.dec256v32(packed, offs, nb, out=out), args.steps, args.warmup)
-    tpf.dec256v32(packed, offs, nb, out=out, err=err)
-    ok = bool(torch.equal(out, vals)) and int(err.item()) == -1
-    sums = {"decoded": checksum(out, dev, T.dist_on), "generated": checksum(vals, dev, T.dist_on)}
-    if T.dist_on:
-        ok = tpf_shard.all_ok(ok, dev)
-    ok = ok and sums["decoded"] == sums["generated"]
-
-    e2e = None
-    if args.e2e and rank == 0:
-        e2e = measure_e2e(packed, offs, nb, vals)
-    # data-movement ceiling of the same access pattern (same kernel, loads
-    # and stores only, no decode) -- outside the timed region
-    _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), 10, 2)
+    dump_outputs(args, rank, {"decoded": out})
+    ok, sums, e2e, probe_ms = None, None, None, None
+    if args.full:
+        tpf.dec256v32(packed, offs, nb, out=out, err=err)
+        ok = bool(torch.equal(out, vals)) and int(err.item()) == -1
+        sums = {"decoded": checksum(out, dev, T.dist_on), "generated": checksum(vals, dev, T.dist_on)}
+        if T.dist_on:
+            ok = tpf_shard.all_ok(ok, dev)
+        ok = ok and sums["decoded"] == sums["generated"]
+        if args.e2e and rank == 0:
+            e2e = measure_e2e(packed, offs, nb, vals)
+        # data-movement ceiling of the same access pattern (same kernel, loads
+        # and stores only, no decode) -- outside the timed region
+        _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), 10, 2)
     avg_ms = float(np.mean(kern_ms))
     alg = pbytes + nb * (1024 + 8) + 8
     achieved = alg / (avg_ms * 1e-3) / 1e9
@@ -546,23 +626,22 @@ def run_c2(args, world, rank, dev, T, c5=False):
     # the box's streaming ceilings (SURVEY §8 d), measured here: rank 0 only,
     # outside the timed region, after the other ranks' work is done
     probes = None
-    if rank == 0 and not args.no_probes:
+    if args.full and rank == 0 and not args.no_probes:
         probes = hbm_probes(dev)
     if rank != 0:
         return None
-    probe = alg / (float(np.mean(probe_ms)) * 1e-3) / 1e9
+    probe = alg / (float(np.mean(probe_ms)) * 1e-3) / 1e9 if probe_ms else None
     roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4), **traffic_fields("c5" if c5 else "c2", nb),
             "kernel": "tpf::dev::k_dec256v32w<StartMode::None>", "kernel_ms_avg": round(avg_ms, 4),
             "kernel_ms_median": round(float(np.median(kern_ms)), 4), "kernel_ms_min": round(float(np.min(kern_ms)), 4),
             "alg_bytes_per_launch": int(alg),
             "alg_bytes_def": "packed block bytes + 1024 B decoded + 8 B offset per block",
-            "probe_GBps": round(probe, 1), "frac_of_probe": round(achieved / probe, 4),
+            "probe_GBps": probe and round(probe, 1), "frac_of_probe": probe and round(achieved / probe, 4),
             "probe_def": "tpfm_probe256v32: the decode kernel's own loads and stores with decoding removed",
             "hbm_probes": probes, "per_rank": per_rank}
     # the CPU baseline is timed at N=1 only (a reported baseline, not a per-rank cost)
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(packed.cpu().numpy(),
-                                                                          offs.cpu().numpy().astype(np.uint64), nb)
+    cpu = None if no_cpu(args, world) else cpu_baseline(packed.cpu().numpy(), offs.cpu().numpy().astype(np.uint64), nb)
     value = nb * 256 * world / (elapsed / args.steps) / 1e9
     cfg = {"workload": ("C5: p4Dec256v32 sharded, 10M blocks x 256 u32 per GPU (80M at 8 GPUs), half bw 8 / half "
                         "bw 16, 10% exceptions" if c5 else
@@ -576,8 +655,8 @@ def run_c2(args, world, rank, dev, T, c5=False):
         cfg["e2e_host_pinned"] = e2e
     data = (f"synthetic (GPU-generated {'C5' if c5 else 'C2'} values: rank r holds blocks [r*nb, (r+1)*nb) of one "
             "counter-keyed global stream; GPU-encoded; full-size decode verified bit-exact on every rank: "
-            + ("ok" if ok else "MISMATCH") + ")")
-    return line(METRIC, value, "G int32/s", world, args.steps, args.warmup, elapsed, "u32", data, cfg, roof, cpu), ok
+            + verdict(ok) + ")")
+    return line(METRIC, value, "G int32/s", world, args.steps, args.warmup, elapsed, "u32", data, cfg, roof, cpu), ok is not False
 
 
 def run_sweep(args, world, rank, dev, T):
@@ -598,25 +677,32 @@ def run_sweep(args, world, rank, dev, T):
         packed = packed_full.clone()
         del packed_full
         _, kern_ms = T.run(lambda: tpf.dec256v32(packed, offs, nb, out=out), args.steps, args.warmup)
-        good = bool(torch.equal(out, vals))
-        _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), max(3, args.steps // 2), 1)
-        ok = ok and good
-        ms, pms = float(np.mean(kern_ms)), float(np.mean(probe_ms))
+        if bw == 32:
+            dump_outputs(args, rank, {"decoded_bw32": out})
+        ms = float(np.mean(kern_ms))
+        good = pms = None
+        if args.full:
+            good = bool(torch.equal(out, vals))
+            _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), max(3, args.steps // 2), 1)
+            ok = ok and good
+            pms = float(np.mean(probe_ms))
         pbytes = packed.numel()
         alg = pbytes + nb * (1024 + 8) + 8
         row = {"bw": bw, "bytes_per_block": round(pbytes / nb, 1), "ms": round(ms, 4), "G_int32_per_s": round(nb * 256 / ms / 1e6, 1),
                "alg_GBps": round(alg / ms / 1e6, 1), "frac": round(alg / ms / 1e6 / HBM_PEAK_GBS, 4),
-               "probe_ms": round(pms, 4), "frac_of_probe": round(pms / ms, 4), "verified": good}
+               "probe_ms": pms and round(pms, 4), "frac_of_probe": pms and round(pms / ms, 4), "verified": good}
         rows.append(row)
         tot_ms += ms
         tot_alg += alg
         if rank == 0:
             log(f"[sweep] bw={bw:2d} B/blk={row['bytes_per_block']:7.1f} ms={ms:.4f} Gint/s={row['G_int32_per_s']:8.1f} "
-                f"alg GB/s={row['alg_GBps']:7.1f} ({row['frac']:.1%} of peak, {row['frac_of_probe']:.1%} of probe)"
-                + ("" if good else " MISMATCH"))
+                f"alg GB/s={row['alg_GBps']:7.1f} ({row['frac']:.1%} of peak"
+                + (f", {row['frac_of_probe']:.1%} of probe)" if pms else ")") + (" MISMATCH" if good is False else ""))
         del vals, packed, offs
     elapsed = time.perf_counter() - t_start
-    if T.dist_on:
+    if not args.full:
+        ok = None
+    elif T.dist_on:
         ok = tpf_shard.all_ok(ok, dev)
     if rank != 0:
         return None
@@ -629,9 +715,10 @@ def run_sweep(args, world, rank, dev, T):
            "nblocks_per_bw": nb, "parallelism": f"shard{world}", "verified": ok}
     res = line("G int32/s device-resident p4Dec256v32, per-width sweep (equal weight)", value, "G int32/s", world,
                32 * args.steps, args.warmup, tot_ms * 1e-3, "u32",
-               "synthetic (GPU-generated per-width values, GPU-encoded; every width verified bit-exact)", cfg, roof, None)
+               "synthetic (GPU-generated per-width values, GPU-encoded; every width verified bit-exact: "
+               + verdict(ok) + ")", cfg, roof, None)
     res["wall_s"] = round(elapsed, 1)
-    return res, ok
+    return res, ok is not False
 
 
 def measure_e2e(packed, offs, nb, vals):
@@ -718,11 +805,10 @@ def run_c3(args, world, rank, dev, T, chained):
     del packed_full
     torch.cuda.synchronize()
     pbytes = packed.numel()
-    mix = block_mix(packed, offs)
-    vb_frac = mix["vbyte_block_frac"]
+    mix = block_mix(packed, offs) if args.full else {}
     if rank == 0:
-        log(f"[bench] c3: {nb} blocks in {time.time() - t0:.1f}s, {pbytes / nb / 256:.3f} B/int, "
-            f"vbyte-mode blocks {vb_frac:.1%}, exception fraction {mix['exception_frac']:.4f}")
+        log(f"[bench] c3: {nb} blocks in {time.time() - t0:.1f}s, {pbytes / nb / 256:.3f} B/int"
+            + (f", vbyte-mode blocks {mix['vbyte_block_frac']:.1%}, exception fraction {mix['exception_frac']:.4f}" if mix else ""))
     out = torch.empty((nb, 256), dtype=torch.int32, device=dev)
     if chained:
         # phase A (block sums + scan), [all-gather of one u32 per rank], phase B
@@ -741,15 +827,18 @@ def run_c3(args, world, rank, dev, T, chained):
     else:
         fn = lambda: tpf.dec256v32(packed, offs, nb, out=out, starts=starts)
     elapsed, kern_ms = T.run(fn, args.steps, args.warmup)
-    # every rank checks its slice of the global list (for a chained list this
-    # verifies the cross-rank exchange: a wrong base shifts every value)
-    ok = bool(torch.equal(out, vals))
-    sums = {"decoded": checksum(out, dev, T.dist_on), "generated": checksum(vals, dev, T.dist_on)}
-    if T.dist_on:
-        ok = tpf_shard.all_ok(ok, dev)
-    ok = ok and sums["decoded"] == sums["generated"]
-    # data-movement probe of the same stream (decode kernel's loads and stores, no decode)
-    _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), 10, 2)
+    dump_outputs(args, rank, {"decoded": out})
+    ok, sums, probe_ms = None, None, None
+    if args.full:
+        # every rank checks its slice of the global list (for a chained list this
+        # verifies the cross-rank exchange: a wrong base shifts every value)
+        ok = bool(torch.equal(out, vals))
+        sums = {"decoded": checksum(out, dev, T.dist_on), "generated": checksum(vals, dev, T.dist_on)}
+        if T.dist_on:
+            ok = tpf_shard.all_ok(ok, dev)
+        ok = ok and sums["decoded"] == sums["generated"]
+        # data-movement probe of the same stream (decode kernel's loads and stores, no decode)
+        _, probe_ms = T.run(lambda: tpf.probe256v32(packed, offs, nb, out), 10, 2)
     avg_ms = float(np.mean(kern_ms))
     alg = pbytes + nb * (1024 + 8 + (0 if chained else 4)) + 8
     per_rank = per_rank_stats(world, dev, avg_ms, alg / (avg_ms * 1e-3) / 1e9)
@@ -763,8 +852,8 @@ def run_c3(args, world, rank, dev, T, chained):
             "kernel_ms_avg": round(avg_ms, 4),
             "kernel": ("k_dsum256v32_lanes (phase A) + run scan (2 small kernels) + k_dec256v32w<Prefix>" if chained
                        else "tpf::dev::k_dec256v32w<StartMode::PerBlock>"),
-            "probe_GBps": round(probe_alg / (float(np.mean(probe_ms)) * 1e-3) / 1e9, 1),
-            "ms_vs_probe": round(avg_ms / float(np.mean(probe_ms)), 3),
+            "probe_GBps": probe_ms and round(probe_alg / (float(np.mean(probe_ms)) * 1e-3) / 1e9, 1),
+            "ms_vs_probe": probe_ms and round(avg_ms / float(np.mean(probe_ms)), 3),
             "probe_def": "tpfm_probe256v32 on the same stream (loads + stores, no decode; no starts read)",
             "per_rank": per_rank}
     cfg = {"workload": "C3: p4D1Dec256v32 " + ("chained list (start0 only)" if chained else "per-block starts")
@@ -774,11 +863,33 @@ def run_c3(args, world, rank, dev, T, chained):
            "checksum_all_ranks": sums,
            "list": "one posting list over all ranks (rank r: blocks [r*nb, (r+1)*nb), values continue rank r-1's)"}
     metric = "G int32/s device-resident p4D1Dec256v32" + (" (chained list)" if chained else "")
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_d1(
+    cpu = None if no_cpu(args, world) else cpu_baseline_d1(
         packed.cpu().numpy(), offs.cpu().numpy().astype(np.uint64), starts.cpu().numpy().view(np.uint32), nb, chained)
     return line(metric, value, "G int32/s", world, args.steps, args.warmup, elapsed, "u32",
                 "synthetic (GPU-generated posting list, counter-keyed by global position, GPU-encoded; decode verified "
-                "bit-exact on every rank: " + ("ok" if ok else "MISMATCH") + ")", cfg, roof, cpu), ok
+                "bit-exact on every rank: " + verdict(ok) + ")", cfg, roof, cpu), ok is not False
+
+
+def c4_line(args, world, first, elapsed, rt_ms, pbytes, per_rank):
+    """C4's line without --full: the timed 32-bit round trip alone (no
+    verification, no separately timed halves, no 64-bit leg, no CPU baseline)."""
+    nb = args.nblocks
+    alg = 2 * (pbytes + nb * (1024 + 8) + 8)
+    rt_gbs = round(alg / (float(np.mean(rt_ms)) * 1e-3) / 1e9, 1)
+    cfg = {"workload": "C4: p4Enc256v32 + p4Dec256v32 round trip, bw 1..32 segments cycling 0/5/10/25% exceptions "
+                       "(--full adds the halves and the p4Enc256v64 + p4Dec256v64 leg)",
+           "nblocks_per_gpu": nb, "parallelism": f"shard{world}", "shard_blocks": [first, first + nb],
+           "verified": None, "bytes_per_block": round(pbytes / nb, 1), "roundtrip_256v64": None}
+    roof = {"bound": "hbm", "achieved": rt_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(rt_gbs / HBM_PEAK_GBS, 4), **traffic_fields("c4", nb),
+            "kernel": "round-trip step: k_enc256v32_plan + run scan (2 small kernels) + k_enc256v32_write + k_dec256v32w<None>",
+            "kernel_ms_avg": round(float(np.mean(rt_ms)), 4), "alg_bytes_per_launch": int(alg),
+            "alg_bytes_def": "encode: 1024 B values + block bytes + 8 B offset; decode: block bytes + 1024 B + 8 B",
+            "per_rank": per_rank}
+    value = nb * 256 * world / (elapsed / args.steps) / 1e9
+    return line("G int32/s device-resident p4Enc256v32+p4Dec256v32 round trip", value, "G int32/s", world, args.steps,
+                args.warmup, elapsed, "u32", "synthetic (GPU-generated, counter-keyed by global position)", cfg, roof,
+                None), True
 
 
 def run_c4(args, world, rank, dev, T):
@@ -802,12 +913,18 @@ def run_c4(args, world, rank, dev, T):
         tpf.dec256v32(p, o, nb, out=dec_out)
 
     elapsed, rt_ms = T.run(rt, args.steps, args.warmup)
+    pbytes = int(state["o"][-1].item())
+    dump_outputs(args, rank, {"packed": state["p"][:pbytes], "offsets": state["o"], "decoded": dec_out})
+    alg_enc = nb * (1024 + 8) + pbytes + 8
+    alg_dec = pbytes + nb * (1024 + 8) + 8
+    per_rank = per_rank_stats(world, dev, float(np.mean(rt_ms)), (alg_enc + alg_dec) / (float(np.mean(rt_ms)) * 1e-3) / 1e9)
+    if not args.full:
+        return c4_line(args, world, first, elapsed, rt_ms, pbytes, per_rank) if rank == 0 else None
     ok = bool(torch.equal(dec_out, vals))
     # the two halves separately (kernel time, HIP events on the launch stream)
     _, enc_ms = T.run(lambda: tpf.enc256v32(vals, out=enc_out), args.steps, 1)
     _, dec_ms = T.run(lambda: tpf.dec256v32(state["p"], state["o"], nb, out=dec_out), args.steps, 1)
-    pbytes = int(state["o"][-1].item())
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_rt(vals.cpu().numpy().view(np.uint32), nb)
+    cpu = None if no_cpu(args, world) else cpu_baseline_rt(vals.cpu().numpy().view(np.uint32), nb)
     del vals, enc_out, dec_out, state
     torch.cuda.empty_cache()
 
@@ -841,9 +958,6 @@ def run_c4(args, world, rank, dev, T):
     del v64, out64, enc64, bufs64
     torch.cuda.empty_cache()
 
-    alg_enc = nb * (1024 + 8) + pbytes + 8
-    alg_dec = pbytes + nb * (1024 + 8) + 8
-    per_rank = per_rank_stats(world, dev, float(np.mean(rt_ms)), (alg_enc + alg_dec) / (float(np.mean(rt_ms)) * 1e-3) / 1e9)
     ok_all = ok and ok64
     if T.dist_on:
         ok_all = tpf_shard.all_ok(ok_all, dev)
@@ -949,14 +1063,17 @@ def run_c3enc(args, world, rank, dev, T):
     elapsed, kern_ms = T.run(enc, args.steps, args.warmup)
     p1, o1 = state["p"], state["o"]
     pbytes = int(o1[-1].item())
-    p2, o2 = tpf.enc256v32(vals, d1=True, starts=starts)
-    ok = bool(torch.equal(o1, o2)) and bool(torch.equal(p1[:pbytes], p2[:pbytes]))
-    del p2, o2
-    out = tpf.dec256v32(p1, o1, nb, starts=starts)
-    ok = ok and bool(torch.equal(out, vals))
-    del out
-    if T.dist_on:
-        ok = tpf_shard.all_ok(ok, dev)
+    dump_outputs(args, rank, {"packed": p1[:pbytes], "offsets": o1})
+    ok = None
+    if args.full:
+        p2, o2 = tpf.enc256v32(vals, d1=True, starts=starts)
+        ok = bool(torch.equal(o1, o2)) and bool(torch.equal(p1[:pbytes], p2[:pbytes]))
+        del p2, o2
+        out = tpf.dec256v32(p1, o1, nb, starts=starts)
+        ok = ok and bool(torch.equal(out, vals))
+        del out
+        if T.dist_on:
+            ok = tpf_shard.all_ok(ok, dev)
     avg_ms = float(np.mean(kern_ms))
     alg = nb * (1024 + 8) + pbytes + 8
     per_rank = per_rank_stats(world, dev, avg_ms, alg / (avg_ms * 1e-3) / 1e9)
@@ -970,14 +1087,14 @@ def run_c3enc(args, world, rank, dev, T):
             "alg_bytes_def": "1024 B values + block bytes + 8 B offset per block (the write pass's second read of the "
                              "values is not counted)",
             "per_rank": per_rank}
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_d1enc(
+    cpu = None if no_cpu(args, world) else cpu_baseline_d1enc(
         vals.cpu().numpy().view(np.uint32), starts.cpu().numpy().view(np.uint32), nb)
     cfg = {"workload": "C3 encode: p4D1Enc256v32 of the C3 Zipf posting list, chained (start0 + the list itself)",
-           "nblocks_per_gpu": nb, "bytes_per_int": round(pbytes / nb / 256, 4), **block_mix(p1, o1),
+           "nblocks_per_gpu": nb, "bytes_per_int": round(pbytes / nb / 256, 4), **(block_mix(p1, o1) if args.full else {}),
            "parallelism": f"shard{world}", "shard_blocks": [first, first + nb], "verified": ok}
     return line("G int32/s device-resident p4D1Enc256v32 (chained posting list)", value, "G int32/s", world, args.steps,
                 args.warmup, elapsed, "u32", "synthetic (GPU-generated C3 posting list; encoding checked against the "
-                "per-block-start encoder and decoded back: " + ("ok" if ok else "MISMATCH") + ")", cfg, roof, cpu), ok
+                "per-block-start encoder and decoded back: " + verdict(ok) + ")", cfg, roof, cpu), ok is not False
 
 
 def cpu_baseline_d1dec64(packed_host, off_host, starts_host, nunits, budget_s=12.0, threads=None):
@@ -1039,11 +1156,14 @@ def run_c3chain64(args, world, rank, dev, T):
                                           ctypes.c_uint64(base), ws.data_ptr(), None, s) == 0
 
     elapsed, kern_ms = T.run(step, args.steps, args.warmup)
-    ok = bool(torch.equal(out, vals))
-    if T.dist_on:
-        ok = tpf_shard.all_ok(ok, dev)
-    _, plain_ms = T.run(lambda: tpf.dec_batch("256v64", packed, offs, nb, 256, starts=starts, out=out.view(-1)), 5, 1)
-    ok = ok and bool(torch.equal(out, vals))
+    dump_outputs(args, rank, {"decoded": out})
+    ok, plain_ms = None, None
+    if args.full:
+        ok = bool(torch.equal(out, vals))
+        if T.dist_on:
+            ok = tpf_shard.all_ok(ok, dev)
+        _, plain_ms = T.run(lambda: tpf.dec_batch("256v64", packed, offs, nb, 256, starts=starts, out=out.view(-1)), 5, 1)
+        ok = ok and bool(torch.equal(out, vals))
     avg_ms = float(np.mean(kern_ms))
     alg = pbytes + nb * (2048 + 8) + 8
     per_rank = per_rank_stats(world, dev, avg_ms, alg / (avg_ms * 1e-3) / 1e9)
@@ -1055,17 +1175,17 @@ def run_c3chain64(args, world, rank, dev, T):
             "kernel": "k_dsum128v64_lanes (phase A, lane per unit) + run scan (u64) + k_dec128v64w<2, Prefix>", "kernel_ms_avg": round(avg_ms, 4),
             "alg_bytes_per_launch": int(alg),
             "alg_bytes_def": "unit bytes + 2048 B decoded + 8 B offset per unit (phase A's read of the stream not counted)",
-            "per_unit_starts_ms_avg": round(float(np.mean(plain_ms)), 4), "per_rank": per_rank}
-    cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_d1dec64(
+            "per_unit_starts_ms_avg": plain_ms and round(float(np.mean(plain_ms)), 4), "per_rank": per_rank}
+    cpu = None if no_cpu(args, world) else cpu_baseline_d1dec64(
         packed.cpu().numpy(), offs.cpu().numpy().astype(np.uint64), starts.cpu().numpy().view(np.uint64), nb)
     cfg = {"workload": "C3 as a 64-bit chained list: p4D1Dec256v64 units of the C3 Zipf gaps as u64 ids above 2^32, "
                        "decoded from start0 alone",
            "nunits_per_gpu": nb, "bytes_per_int": round(pbytes / nb / 256, 4), "parallelism": f"shard{world}",
            "shard_units": [first, first + nb], "verified": ok,
-           "per_unit_starts_G_int64_per_s": round(nb * 256 / (float(np.mean(plain_ms)) * 1e-3) / 1e9, 2)}
+           "per_unit_starts_G_int64_per_s": plain_ms and round(nb * 256 / (float(np.mean(plain_ms)) * 1e-3) / 1e9, 2)}
     return line("G int64/s device-resident p4D1Dec256v64 (chained list)", value, "G int64/s", world, args.steps,
                 args.warmup, elapsed, "u64", "synthetic (GPU-generated 64-bit posting list, GPU-encoded; chained decode "
-                "verified bit-exact on every rank: " + ("ok" if ok else "MISMATCH") + ")", cfg, roof, cpu), ok
+                "verified bit-exact on every rank: " + verdict(ok) + ")", cfg, roof, cpu), ok is not False
 
 
 def cpu_abtest_c1(vals_host, blk_host, blen, n):
@@ -1105,8 +1225,11 @@ def run_c1(args, world, rank, dev, T):
     packed, offs = tpf.enc_batch("32", vals, nb, n)
     out = torch.empty_like(vals)
     elapsed, kern_ms = T.run(lambda: tpf.dec_batch("32", packed, offs, nb, n, out=out), args.steps, args.warmup)
-    ok = bool(torch.equal(out, vals))
-    _, enc_ms = T.run(lambda: tpf.enc_batch("32", vals, nb, n), max(2, args.steps // 4), 1)
+    dump_outputs(args, rank, {"decoded": out.view(nb, n)})
+    ok, enc_ms = None, None
+    if args.full:
+        ok = bool(torch.equal(out, vals))
+        _, enc_ms = T.run(lambda: tpf.enc_batch("32", vals, nb, n), max(2, args.steps // 4), 1)
     pbytes = int(packed.numel())
     avg_ms = float(np.mean(kern_ms))
     alg = pbytes + nb * (n * 4 + 8) + 8
@@ -1120,15 +1243,16 @@ def run_c1(args, world, rank, dev, T):
             "kernel": "tpf::dev::k_dec_h32w (windowed horizontal p4Dec32 batch: 64-block wave runs, windows staged whole, lane-parsed headers)",
             "per_rank": per_rank}
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if not no_cpu(args, world):
         blen = int(offs[1].item())
         blk = np.concatenate([packed[:blen].cpu().numpy(), np.zeros(64, np.uint8)])  # + the reference's read slack
         cpu = cpu_abtest_c1(vals[:n].cpu().numpy().view(np.uint32).copy(), blk, blen, n)
     cfg = {"workload": "C1: p4Enc32/p4Dec32, n=127, bw 8, 0% exceptions (configs[0]); device batch of n=127 blocks",
            "nblocks_per_gpu": nb, "bytes_per_block": round(pbytes / nb, 2), "verified": ok,
-           "enc32_G_int32_per_s": round(nb * n / (float(np.mean(enc_ms)) * 1e-3) / 1e9, 2), "parallelism": f"shard{world}"}
+           "enc32_G_int32_per_s": enc_ms and round(nb * n / (float(np.mean(enc_ms)) * 1e-3) / 1e9, 2),
+           "parallelism": f"shard{world}"}
     return line("G int32/s device-resident p4Dec32 (n=127)", value, "G int32/s", world, args.steps, args.warmup,
-                elapsed, "u32", "synthetic (GPU-generated uniform [0,255], GPU-encoded)", cfg, roof, cpu), ok
+                elapsed, "u32", "synthetic (GPU-generated uniform [0,255], GPU-encoded)", cfg, roof, cpu), ok is not False
 
 
 # ------------------------------------------------------------ launcher
@@ -1178,12 +1302,21 @@ def main():
     ap.add_argument("--nblocks", type=int, default=10_000_000, help="blocks per GPU (shard)")
     ap.add_argument("--exc", type=float, default=10.0)
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c3chain", "c3enc", "c3chain64", "c4", "c5", "sweep"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e2e", action="store_true", help="c2: also measure the pinned host-memory path")
-    ap.add_argument("--no-probes", action="store_true", help="c2: skip the in-run HBM read/write/copy probes")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: verify the outputs at full size, run the data-movement probes, the "
+                         "separately timed parts and the CPU baselines (off: those fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a seeded sample and the checksum of what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--e2e", action="store_true", help="--full, c2: also measure the pinned host-memory path")
+    ap.add_argument("--no-probes", action="store_true", help="--full, c2: skip the in-run HBM read/write/copy probes")
     ap.add_argument("--selftest", action="store_true",
                     help="launcher + process-group plumbing with a CPU stand-in step (gloo, no GPU)")
     args = ap.parse_args()
+    if args.e2e and not args.full:
+        ap.error("--e2e measures beside the timed steps: give --full with it")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))

@@ -14,7 +14,7 @@ O, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
 tag, wls = sys.argv[1], sys.argv[2:]
 stats = os.path.join(P, f"{tag}_kernel_stats.txt")
 have = open(stats).read() if os.path.exists(stats) else (
-    f"# {tag}: rocprofv3 --kernel-trace --stats of python bench.py --workload WL --steps 20 --warmup 5 --no-cpu-baseline\n"
+    f"# {tag}: rocprofv3 --kernel-trace --stats of python bench.py --full --workload WL --steps 20 --warmup 5 --no-cpu-baseline\n"
     "# (scripts/gpu.sh prof:WL), one section per workload: kernel, calls, average ms, total ms.\n")
 for wl in wls:
     for src, dst in ((f"{tag}_bench_{wl}.json", f"{tag}_bench_{wl}.json"), (f"{tag}_{wl}_under_rocprof.json", f"{tag}_{wl}_under_rocprof.json")):

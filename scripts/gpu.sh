@@ -27,11 +27,11 @@ for step in "$@"; do
       tail -1 $O/${T}_smoke.log ;;
     bench)
       wl=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""
-      timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --workload $wl ${a//,/ } > $O/${T}_bench_$wl.json 2> $O/${T}_bench_$wl.err || fail "bench $wl" $? $O/${T}_bench_$wl.err
+      timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --full --workload $wl ${a//,/ } > $O/${T}_bench_$wl.json 2> $O/${T}_bench_$wl.err || fail "bench $wl" $? $O/${T}_bench_$wl.err
       tail -1 $O/${T}_bench_$wl.json ;;
     prof)
       wl=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""
-      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/${T}_${wl}_prof -o run --output-format csv -- python3 $R/bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > $O/${T}_${wl}_under_rocprof.json 2> $O/${T}_${wl}_prof.err) || fail "prof $wl" $? $O/${T}_${wl}_prof.err
+      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/${T}_${wl}_prof -o run --output-format csv -- python3 $R/bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline ${a//,/ } > $O/${T}_${wl}_under_rocprof.json 2> $O/${T}_${wl}_prof.err) || fail "prof $wl" $? $O/${T}_${wl}_prof.err
       tail -1 $O/${T}_${wl}_under_rocprof.json
       python3 -c "
 import csv,glob,sys
@@ -43,7 +43,7 @@ for f in glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True):
       wl=$rest
       [ -f $O/pmc_traffic.json ] || cp profiles/pmc_traffic.json $O/pmc_traffic.json
       for c in FETCH_SIZE WRITE_SIZE; do
-        (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --pmc $c -d $O/pmc_${wl}_$c -o run --output-format csv -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_pmc_${wl}_$c.json 2>&1) || fail "pmc $wl $c" $? $O/bench_pmc_${wl}_$c.json
+        (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --pmc $c -d $O/pmc_${wl}_$c -o run --output-format csv -- python3 $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_pmc_${wl}_$c.json 2>&1) || fail "pmc $wl $c" $? $O/bench_pmc_${wl}_$c.json
       done
       python3 scripts/pmc_traffic.py $wl $O/pmc_${wl}_FETCH_SIZE/run_counter_collection.csv $O/pmc_${wl}_WRITE_SIZE/run_counter_collection.csv 10000000 $O/pmc_traffic.json ${LABEL:-$T} || fail "pmc_traffic $wl" $?
       if [ $wl = c4 ]; then
@@ -56,7 +56,7 @@ for f in glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True):
          for ev in ${ENVS:-none}; do
           if [ $lib = tree ]; then unset TPF_LIB; else export TPF_LIB=$R/$lib; fi
           n=$(basename $lib .so); [ $ev = none ] || n=${n}_${ev//=/}
-          timeout -k 10 240 env ${ev/#none/TPF_AB=0} python bench.py --workload $wl --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-probes ${BARGS} > $O/${T}_ab_${wl}_${n}_$i.json 2> $O/${T}_ab_${wl}_${n}_$i.err || fail "ab $n" $? $O/${T}_ab_${wl}_${n}_$i.err 5
+          timeout -k 10 240 env ${ev/#none/TPF_AB=0} python bench.py --full --workload $wl --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-probes ${BARGS} > $O/${T}_ab_${wl}_${n}_$i.json 2> $O/${T}_ab_${wl}_${n}_$i.err || fail "ab $n" $? $O/${T}_ab_${wl}_${n}_$i.err 5
           python -c "import json,sys; d=json.load(open(sys.argv[1])); c=d['config']; r=d['roofline']; print(sys.argv[3], sys.argv[2], d['value'], 'ms', r.get('kernel_ms_avg'), 'verified', c.get('verified'), {k: v for k, v in c.items() if k.endswith('per_s')})" $O/${T}_ab_${wl}_${n}_$i.json $n $wl
          done
         done

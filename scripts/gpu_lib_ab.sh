@@ -3,11 +3,12 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
 WL=${WL:-c4}
+O=${OUT:-$R/bench_out}; mkdir -p $O  # where the result lines go
 for i in $(seq ${ROUNDS:-2}); do
   for lib in base new; do
     if [ $lib = base ]; then export TPF_LIB=$R/abtmp/base.so; else unset TPF_LIB; fi
-    timeout -k 10 200 python bench.py --workload $WL --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > gpurun_out/ab_${lib}_$i.json 2> gpurun_out/ab_${lib}_$i.err || { echo "$lib rc=$?"; tail -5 gpurun_out/ab_${lib}_$i.err; exit 1; }
-    python - gpurun_out/ab_${lib}_$i.json $lib <<'PY'
+    timeout -k 10 200 python bench.py --full --workload $WL --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > $O/ab_${lib}_$i.json 2> $O/ab_${lib}_$i.err || { echo "$lib rc=$?"; tail -5 $O/ab_${lib}_$i.err; exit 1; }
+    python - $O/ab_${lib}_$i.json $lib <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); c = d['config']
 extra = {k: v for k, v in c.items() if k.endswith('per_s')}

@@ -105,7 +105,7 @@ def test_bench_data_same_on_gpu_and_cpu():
 @pytest.mark.timeout(400)
 @pytest.mark.parametrize("workload", ["c3chain", "c3", "c2", "c5", "c3chain64", "c3enc", "c4"])
 def test_bench_two_ranks_one_gpu(workload, tmp_path):
-    """bench.py --gpus 2 (launcher, two ranks sharing cuda:0 over gloo: RCCL
+    """bench.py --gpus 2 --full (launcher, two ranks sharing cuda:0 over gloo: RCCL
     refuses two ranks on one device) on a small shard: rank 1's slice
     continues rank 0's list, the chained decode's exchange rebuilds it, and
     the printed `verified` is computed on every rank."""
@@ -118,7 +118,7 @@ def test_bench_two_ranks_one_gpu(workload, tmp_path):
     env = dict(os.environ, TPF_BENCH_SAME_GPU="1", TPF_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", workload,
-                        "--nblocks", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-probes"],
+                        "--nblocks", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-probes"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -128,6 +128,36 @@ def test_bench_two_ranks_one_gpu(workload, tmp_path):
     if "checksum_all_ranks" in res["config"]:
         assert res["config"]["checksum_all_ranks"]["decoded"] == res["config"]["checksum_all_ranks"]["generated"]
     assert res["config"].get("shard_blocks", res["config"].get("shard_units")) == [0, 20000]
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A run without --full times its steps and nothing else (verified, the
+    probes and the CPU baseline are null), --steps is the number of timed
+    steps, and --dump-outputs writes the last step's decode: the dumped rows
+    are the generator's rows and the sum is the whole array's."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench_data as B
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nb = 30_000  # above the dump's row budget: the rows are a sample
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--nblocks", str(nb), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["unit"] == "G int32/s"
+    assert res["value"] == pytest.approx(nb * 256 / res["ms_per_step"] / 1e6, rel=1e-2)
+    assert res["config"]["verified"] is None and res["cpu_baseline"] is None
+    assert res["roofline"]["probe_GBps"] is None and res["roofline"]["hbm_probes"] is None
+    assert sorted(os.listdir(tmp_path)) == ["decoded.npy", "decoded_rows.npy", "decoded_sum.npy"]
+    got, rows, tot = (np.load(tmp_path / f) for f in ("decoded.npy", "decoded_rows.npy", "decoded_sum.npy"))
+    assert got.dtype == np.float64 and got.shape == (len(rows), 256) and 0 < len(rows) < nb
+    vals = B.gen_c2(nb, 10.0, 42, "cpu")[0].numpy().view(np.uint32)
+    np.testing.assert_array_equal(got, vals[rows.astype(np.int64)].astype(np.float64))
+    assert int(tot[0]) + (int(tot[1]) << 32) == int(vals.sum(dtype=np.uint64))
 
 
 @pytest.mark.parametrize("misalign", [0, 1, 3])
