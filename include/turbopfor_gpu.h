@@ -177,6 +177,54 @@ size_t tpf_p4ndec256v32_workspace_size(uint64_t n);
 int tpf_p4ndec256v32(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t n, int d1, uint32_t start0,
                      uint32_t *d_out, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- many lists in one call ------------------------------------------------
+ * An inverted index is a very large number of posting lists of very different
+ * lengths, each stored as the n-variant stream above: a caller's chain of
+ * p4{,D1}Enc256v32 over the full 256-value blocks and p4{,D1}Enc32 over the
+ * last n % 256 values (reference include/turbopfor.h:9, :33), every block's
+ * start the value before it.  tpf_p4ndec256v32_lists decodes nlists such
+ * streams laid end to end in ONE submission (replacing a loop of
+ * tpf_p4ndec256v32 calls, a handful of launches per list).
+ *   - List layout (CSR form): d_list_ptr[0..nlists] is non-decreasing; list j
+ *     has n_j = ptr[j+1] - ptr[j] values, written to d_out + ptr[j], so the
+ *     output is dense and ragged.  ptr[0] need not be 0.  Empty lists are
+ *     allowed anywhere, any number in a row.
+ *   - Units: list j occupies units_j = n_j/256 + (n_j%256 != 0) consecutive
+ *     units of the stream, in list order: its full 256v32 blocks, then one
+ *     p4{,D1}Enc32 block of n_j % 256 values -- the stream tpf_p4nenc256v32
+ *     writes for one list, the lists concatenated.
+ *   - Offsets: d_off[0..nunits] are the units' byte offsets under the OFFSETS
+ *     CONTRACT above (nunits + 1 readable entries); nunits must equal the sum
+ *     of units_j.
+ *   - Delta-1: with d1 != 0 list j is chained from d_start0[j] (the value
+ *     before its first); d_start0 == NULL means 0 for every list.  Arithmetic
+ *     is mod 2^32 as in the reference's applyDelta1_256.  With d1 == 0
+ *     d_start0 is ignored.
+ *   - Output bounds: out_values is the capacity of d_out in values; nothing is
+ *     written at or past it, and nothing outside [ptr[j], ptr[j+1]) for any j.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       < nunits          the first unit whose parse disagrees with its
+ *                         offsets (as everywhere else);
+ *       nunits + j        the first list j with ptr[j+1] < ptr[j] or
+ *                         ptr[j+1] > out_values;
+ *       nunits + nlists   the lists' unit counts do not add up to nunits.
+ *     For either list-structure error the device decodes nothing and writes
+ *     nothing to d_out.
+ *   - TPF_EINVAL: a null d_in / d_off / d_list_ptr / d_out / d_ws, ws_bytes
+ *     below tpf_p4ndec256v32_lists_workspace_size(nunits, nlists), nunits or
+ *     nlists above 0x7FFFFFFF.  nlists == 0 or nunits == 0 is a successful
+ *     no-op that still sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy (the structure is checked on the device), so the
+ *     call sits inside a caller's pipeline like the other entries.  There is
+ *     no limit on a list's length other than nunits.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_p4ndec256v32_lists_workspace_size(uint64_t nunits, uint64_t nlists);
+int tpf_p4ndec256v32_lists(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                           const uint64_t *d_list_ptr, uint64_t nlists, int d1, const uint32_t *d_start0, uint32_t *d_out,
+                           uint64_t out_values, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

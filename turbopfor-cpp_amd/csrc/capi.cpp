@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/turbopfor_gpu.h"
+#include "p4_lists.h"
 #include "tpf_kernels.h"
 
 #include <algorithm>
@@ -465,6 +466,29 @@ int tpf_p4ndec256v32(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     hipError_t e = tpf::launch_err_merge(reinterpret_cast<unsigned long long *>(d_err), reinterpret_cast<unsigned long long *>(tail_err),
                                          nfull, s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32");
+}
+
+// ---- many lists in one call: each list an n-variant stream, laid end to end
+size_t tpf_p4ndec256v32_lists_workspace_size(uint64_t nunits, uint64_t nlists) { return tpf::lists_workspace(nunits, nlists); }
+
+int tpf_p4ndec256v32_lists(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                           uint64_t nlists, int d1, const uint32_t * d_start0, uint32_t * d_out, uint64_t out_values, void * d_ws,
+                           size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (int rc = check_device())
+        return rc;
+    if (nunits && nlists && (!d_in || !d_off || !d_list_ptr || !d_out || !d_ws))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: null pointer");
+    if (nunits && nlists && ws_bytes < tpf_p4ndec256v32_lists_workspace_size(nunits, nlists))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: workspace too small");
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: nunits and nlists are limited to 0x7FFFFFFF");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_dec(d_in, in_bytes, d_off, nunits, d_list_ptr, nlists, d1 != 0, d1 ? d_start0 : nullptr, d_out,
+                                         out_values, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists");
 }
 
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)

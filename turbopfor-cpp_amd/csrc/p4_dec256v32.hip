@@ -4,6 +4,7 @@
 #include "p4_dec256v32.h"
 #include "tpf_kernels.h"
 
+#include "p4_lists.h"
 #include "p4_scan.h"
 
 // Phase-A ablation (measurement builds only, scripts/chain_phase_probe.py;
@@ -84,9 +85,29 @@ template <uint32_t WB>
 constexpr uint32_t kDsumLim = WB + 28u;
 static_assert(kDsumLim<16384u> / 4u + 9u <= (16384u + 64u) / 4u, "clamped phase-A reads stay in the wave's window");
 
-template <uint32_t WB>
-__global__ __launch_bounds__(256, 2) void k_dsum256v32_lanes(const DecArgs A)
+// LISTS (the many-lists decode, p4_lists.h): the units of a lists stream
+// whose record carries kRecTail are p4Enc32 tails.  They are never parsed as
+// 256v32: their lanes start out done with sum 0 (a tail is the last unit of
+// its list, so its sum enters no start), and the kernel does nothing at all
+// when the plan pass refused the list structure.
+struct DsumNoLists
 {
+    static constexpr bool lists = false;
+};
+struct DsumLists
+{
+    static constexpr bool lists = true;
+    const uint32_t * rec;  // one record per unit (kRecTail)
+    const ListsHdr * hdr;  // go / no-go
+    uint64_t nlists;
+};
+
+template <uint32_t WB, class X>
+__device__ __forceinline__ void dsum256v32_lanes(const DecArgs & A, const X & L)
+{
+    if constexpr (X::lists)
+        if (!lists_go(L.hdr, A.nblocks))
+            return;
     static_assert(WB % 1024u == 0u && WB + 64u >= kSlotBytes + 4u * kWaveScratchU32, "the window also hosts the fallback's slot and scratch");
     constexpr uint32_t NL = WB / 1024u; // 16-byte loads per lane per pass
     __shared__ uint32_t tab[33 * kSumTabRow];
@@ -122,8 +143,17 @@ __global__ __launch_bounds__(256, 2) void k_dsum256v32_lanes(const DecArgs A)
         }
     };
 
+    auto load_run = [&](DsumRun & R, uint64_t r) {
+        R.load(A, r, t, WB);
+        if constexpr (X::lists)
+            if (R.valid && (L.rec[R.first + t] & kRecTail) != 0u)
+            {
+                R.fb = false;
+                R.done = true;
+            }
+    };
     DsumRun cur;
-    cur.load(A, run, t, WB);
+    load_run(cur, run);
     uint32_t sumv = 0u;
     dsum_pass<WB>(A, cur, wbase, span, avail); // the lead lane of a fresh run is pending or every lane declined
     issue();
@@ -161,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void k_dsum256v32_lanes(const DecArgs A)
             last = nrun >= nruns;
             if (!last)
             {
-                nxt.load(A, nrun, t, WB);
+                load_run(nxt, nrun);
                 if (!dsum_pass<WB>(A, nxt, wbase, span, avail))
                     span = 0u; // every block of that run declined: nothing to stage
             }
@@ -242,6 +272,19 @@ __global__ __launch_bounds__(256, 2) void k_dsum256v32_lanes(const DecArgs A)
     }
 }
 
+template <uint32_t WB>
+__global__ __launch_bounds__(256, 2) void k_dsum256v32_lanes(const DecArgs A)
+{
+    dsum256v32_lanes<WB>(A, DsumNoLists{});
+}
+
+// phase A of the many-lists decode: the same sums, tails skipped
+template <uint32_t WB>
+__global__ __launch_bounds__(256, 2) void k_dsum256v32_lists(const DecArgs A, const DsumLists L)
+{
+    dsum256v32_lanes<WB>(A, L);
+}
+
 } // namespace tpf::dev
 
 namespace tpf
@@ -314,6 +357,27 @@ hipError_t launch_d1chain_sums(const uint8_t * in, uint64_t in_bytes, const uint
     if (e != hipSuccess)
         return e;
     return launch_run_scan_u32(rs.tot, (nblocks + dev::kSumRun - 1u) / dev::kSumRun, rs.pre, rs.tile, total, stream);
+}
+
+// Phase A over a lists stream (p4_lists.hip): the chained decode's workspace
+// layout and run scan, tails skipped through the unit records.
+hipError_t launch_lists_sums(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint32_t * rec,
+                             const dev::ListsHdr * hdr, uint64_t nlists, void * ws, ChainView * view, unsigned long long * err,
+                             hipStream_t stream)
+{
+    auto * sums = static_cast<uint32_t *>(ws);
+    const RunScanWs<uint32_t> rs = RunScanWs<uint32_t>::carve(static_cast<uint8_t *>(ws) + al256(nunits * 4u), chain_runs(nunits));
+    dev::DecArgs A{in, in_bytes, off, nunits, nullptr, nullptr, 0u, sums, err};
+    A.run_tot = rs.tot;
+    *view = ChainView{sums, rs.pre, rs.tile};
+    constexpr uint64_t per_wg = 4ull * dev::kSumRun;
+    const uint64_t wgs = std::min<uint64_t>((nunits + per_wg - 1) / per_wg, grid_cap(stream, kDsumWgPerCu));
+    hipLaunchKernelGGL((dev::k_dsum256v32_lists<kDsumWindow>), dim3(static_cast<uint32_t>(wgs)), dim3(256), 0, stream, A,
+                       dev::DsumLists{rec, hdr, nlists});
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    return launch_run_scan_u32(rs.tot, (nunits + dev::kSumRun - 1u) / dev::kSumRun, rs.pre, rs.tile, nullptr, stream);
 }
 
 hipError_t launch_d1chain_decode(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nblocks, uint32_t * out,

@@ -1,0 +1,59 @@
+// p4_lists.h -- decode of many posting lists laid end to end in one call
+// (tpf_p4ndec256v32_lists, include/turbopfor_gpu.h): what the plan pass leaves
+// in the workspace for the kernels after it (internal).
+//
+// Passes (p4_lists.hip): plan (one thread per list: unit
+// counts, structure check) -> run scan of the unit counts (p4_scan.h) -> heads
+// (unit bases, one record per unit) -> [delta-1: phase A over every full block
+// (k_dsum256v32_lists, p4_dec256v32.hip), its run scan, one prefix per list]
+// -> decode (k_lists_dec).  Nothing comes back to the host in between: every
+// kernel after the plan reads the header below and does nothing when the list
+// structure was refused.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace tpf::dev
+{
+
+// Unit record (u32 per unit of the stream): the first unit of list j carries
+// j + 1 in the low 31 bits (0: not a head), the p4Enc32 tail of a list carries
+// kRecTail.  A tail-only list is both.  A wave finds the list of every unit of
+// its run from one search for the run's first unit and a max-scan of the heads.
+constexpr uint32_t kRecTail = 0x80000000u;
+constexpr uint32_t kRecList = 0x7FFFFFFFu;
+
+struct ListsHdr
+{
+    unsigned long long bad;   // first list j with ptr[j+1] < ptr[j] or ptr[j+1] > out_values (~0: none)
+    unsigned long long total; // sum of the lists' unit counts
+};
+
+// go / no-go: the structure is sound and the unit counts add up to nunits
+__device__ __forceinline__ bool lists_go(const ListsHdr * h, uint64_t nunits)
+{
+    return h->bad == ~0ull && h->total == nunits;
+}
+
+} // namespace tpf::dev
+
+namespace tpf
+{
+
+size_t lists_workspace(uint64_t nunits, uint64_t nlists);
+hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                            uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
+                            unsigned long long * err, hipStream_t s);
+// phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
+// `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
+// units skipped; *view = where phase B finds them
+struct ChainView
+{
+    const uint32_t *sums = nullptr, *pre = nullptr, *tile = nullptr;
+};
+hipError_t launch_lists_sums(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint32_t * rec,
+                             const dev::ListsHdr * hdr, uint64_t nlists, void * ws, ChainView * view, unsigned long long * err,
+                             hipStream_t stream);
+
+} // namespace tpf

@@ -120,6 +120,13 @@ def lib():
             L.tpf_d1dec64_chain_decode.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]
             for name in ("tpf_d1dec64_chained", "tpf_d1dec64_chain_sums", "tpf_d1dec64_chain_decode"):
                 getattr(L, name).restype = ctypes.c_int
+        # the many-lists decode: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_p4ndec256v32_lists"):
+            L.tpf_p4ndec256v32_lists_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_p4ndec256v32_lists_workspace_size.restype = ctypes.c_size_t
+            L.tpf_p4ndec256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp,
+                                                 ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_p4ndec256v32_lists.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -450,4 +457,52 @@ def decn256v32(packed, offsets, n, d1=False, start0=0, out=None, err=None):
     _check(L.tpf_p4ndec256v32(_ptr(packed), packed.numel(), _ptr(offsets), n, int(bool(d1)),
                               ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), _ptr(ws), ws_bytes, _ptr(err),
                               _stream(torch)))
+    return out
+
+
+# ---- many lists in one call (include/turbopfor_gpu.h tpf_p4ndec256v32_lists) ----
+def lists_units(list_ptr):
+    """Per-list unit counts and unit bases of a lists stream: list j of
+    n_j = list_ptr[j+1] - list_ptr[j] values holds n_units(n_j) units starting
+    at unit base[j].  list_ptr: a CPU tensor, numpy array or sequence of
+    nlists + 1 non-decreasing integers.  Returns (units, base) as int64 numpy
+    arrays of nlists and nlists + 1 entries (base[nlists] = the stream's unit
+    count).  Pure host code: the library is not loaded."""
+    import numpy as np
+
+    if hasattr(list_ptr, "detach"):
+        list_ptr = list_ptr.detach().cpu().numpy()
+    p = np.asarray(list_ptr).astype(np.int64).reshape(-1)
+    if p.size == 0:
+        raise ValueError("list_ptr holds nlists + 1 entries")
+    n = np.diff(p)
+    if (n < 0).any():
+        raise ValueError("list_ptr must be non-decreasing")
+    units = n // 256 + (n % 256 != 0)
+    base = np.zeros(p.size, dtype=np.int64)
+    np.cumsum(units, out=base[1:])
+    return units.astype(np.int64), base
+
+
+def decn256v32_lists(packed, offsets, list_ptr, d1=False, start0=None, out=None, err=None, ws=None):
+    """Decode many lists laid end to end in one call: list j is an
+    encn256v32-layout stream of list_ptr[j+1] - list_ptr[j] values, its units
+    following list j-1's; offsets: int64 [nunits + 1].  list_ptr: int64 CUDA
+    tensor [nlists + 1] (CSR form); start0: optional int32 CUDA tensor
+    [nlists] of each list's preceding value (d1 only; None = 0).  out: int32
+    CUDA tensor whose numel() is the capacity in values (default: sized from
+    list_ptr[-1], which costs a device-to-host read; pass out to stay
+    asynchronous).  Values land at out[list_ptr[j]:list_ptr[j+1]]."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    if out is None:
+        out = torch.empty(int(list_ptr[-1].item()), dtype=torch.int32, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_p4ndec256v32_lists_workspace_size(nunits, nlists))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_p4ndec256v32_lists(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), nlists, int(bool(d1)),
+                                    _ptr(start0), _ptr(out), out.numel(), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
