@@ -225,6 +225,66 @@ int tpf_p4ndec256v32_lists(const uint8_t *d_in, uint64_t in_bytes, const uint64_
                            const uint64_t *d_list_ptr, uint64_t nlists, int d1, const uint32_t *d_start0, uint32_t *d_out,
                            uint64_t out_values, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* tpf_p4nenc256v32_lists is the mirror: it PRODUCES that stream from nlists
+ * posting lists in ONE submission (replacing a loop of tpf_p4nenc256v32 calls,
+ * or a gather into aligned copies around the batch encoders).  Its d_out,
+ * d_off, d_list_ptr and d_start0 feed tpf_p4ndec256v32_lists unchanged.
+ *   - Input (CSR form): d_list_ptr[0..nlists] is non-decreasing; list j is the
+ *     n_j = ptr[j+1] - ptr[j] values at d_in + ptr[j], so the input is dense
+ *     and ragged, positions only 4-byte aligned.  ptr[0] need not be 0.  Empty
+ *     lists are allowed anywhere, any number in a row.  in_values is the
+ *     readable length of d_in in values: nothing at or past it is read, and
+ *     nothing outside [ptr[j], ptr[j+1]) for any j -- in particular never the
+ *     value before a list.
+ *   - Output: list j's stream is byte for byte what
+ *     tpf_p4nenc256v32(d_in + ptr[j], n_j, d1, start0[j], ...) writes: its full
+ *     p4{,D1}Enc256v32 blocks, then one p4{,D1}Enc32 block of n_j % 256 values;
+ *     the lists concatenated in list order with no padding between them.
+ *     d_off[0..nunits] receives the units' byte offsets: d_off[0] = 0 and
+ *     d_off[nunits] is the stream's length.
+ *   - Delta-1: with d1 != 0 the first unit of list j starts from d_start0[j]
+ *     (the value before its first; d_start0 == NULL means 0 for every list),
+ *     every later unit, the tail included, from the input value before it; a
+ *     tail-only list's tail starts from d_start0[j].  Arithmetic is mod 2^32.
+ *     With d1 == 0 d_start0 is ignored.
+ *   - nunits is the capacity of d_off in units (nunits + 1 writable entries)
+ *     and must equal the sum of units_j = n_j/256 + (n_j%256 != 0).
+ *   - Capacity is checked on the device, once the sizes are known: when the
+ *     stream is longer than out_cap nothing is written to d_out, but d_off is
+ *     still filled completely and correctly, so d_off[nunits] tells the caller
+ *     what to allocate.  Nothing is ever written at or past d_out + out_cap,
+ *     nor before d_out.  tpf_p4nenc256v32_lists_bound(nvalues, nlists) is
+ *     advice, a capacity that always suffices, not a precondition.  It sums the
+ *     per-unit bounds of the batch encoders -- 1800 B per full block (at most
+ *     8 B per value), 128 + 8 r B per tail of r values -- over the worst way
+ *     nvalues values can fall into nlists lists: T = min(nlists, nvalues)
+ *     tails, as few full blocks as the T tails (255 values each at most) leave,
+ *         8 nvalues + 128 T - floor(248 max(0, nvalues - 255 T - 255) / 256) + 64
+ *     (the block count taken without rounding up, which keeps the bound
+ *     non-decreasing in both arguments).
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       nunits + j          the first list j with ptr[j+1] < ptr[j] or
+ *                           ptr[j+1] > in_values;
+ *       nunits + nlists     the lists' unit counts do not add up to nunits;
+ *       nunits + nlists + 1 out_cap is below the stream's length.
+ *     For either list-structure error neither d_out nor d_off is written.  An
+ *     encoder has no per-unit parse error: values < nunits are never reported.
+ *   - TPF_EINVAL: a null d_list_ptr, d_off or d_ws when nlists is non-zero, a
+ *     null d_in or d_out when nunits is non-zero, ws_bytes below
+ *     tpf_p4nenc256v32_lists_workspace_size(nunits, nlists), nunits or nlists
+ *     above 0x7FFFFFFF.  nlists == 0, or nunits == 0 with every list empty, is
+ *     a successful no-op that sets d_off[0] = 0 and d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy, and a fixed number of launches whatever the number
+ *     of lists and their lengths.
+ * d_ws: device workspace, at least 8-byte aligned. */
+uint64_t tpf_p4nenc256v32_lists_bound(uint64_t nvalues, uint64_t nlists);
+size_t tpf_p4nenc256v32_lists_workspace_size(uint64_t nunits, uint64_t nlists);
+int tpf_p4nenc256v32_lists(const uint32_t *d_in, uint64_t in_values, const uint64_t *d_list_ptr, uint64_t nlists, int d1,
+                           const uint32_t *d_start0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_off, uint64_t nunits,
+                           void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

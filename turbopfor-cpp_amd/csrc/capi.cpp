@@ -491,6 +491,46 @@ int tpf_p4ndec256v32_lists(const uint8_t * d_in, uint64_t in_bytes, const uint64
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists");
 }
 
+// The per-unit bounds (1800 B per full block, tpf_enc_bound(TPF_FMT_32, 1, r)
+// = 128 + 8 r per tail of r values) summed over the worst partition: a full
+// block costs at most 8 B per value, so a stream of K full blocks and T tails
+// is bounded by 8 nvalues - 248 K + 128 T; T <= min(nlists, nvalues) and the T
+// tails hold at most 255 T values, so K >= (nvalues - 255 T) / 256, taken
+// without rounding up ((x - 255) / 256 <= ceil(x / 256)) so that the bound
+// never decreases with nvalues (the exact maximum does: one list of 255
+// values is bounded by 2,168 B, of 256 by 1,800).
+uint64_t tpf_p4nenc256v32_lists_bound(uint64_t nvalues, uint64_t nlists)
+{
+    const uint64_t T = std::min(nlists, nvalues);
+    const uint64_t x = nvalues > 255u * T ? nvalues - 255u * T : 0u;
+    const uint64_t k256 = x > 255u ? x - 255u : 0u; // 256 x the full blocks no partition can avoid
+    return 8u * nvalues + 128u * T - (248u * k256) / 256u + 64u;
+}
+
+size_t tpf_p4nenc256v32_lists_workspace_size(uint64_t nunits, uint64_t nlists) { return tpf::lists_enc_workspace(nunits, nlists); }
+
+int tpf_p4nenc256v32_lists(const uint32_t * d_in, uint64_t in_values, const uint64_t * d_list_ptr, uint64_t nlists, int d1,
+                           const uint32_t * d_start0, uint8_t * d_out, uint64_t out_cap, uint64_t * d_off, uint64_t nunits, void * d_ws,
+                           size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (int rc = check_device())
+        return rc;
+    if (nlists && (!d_list_ptr || !d_off || !d_ws))
+        return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: null pointer");
+    if (nlists && nunits && (!d_in || !d_out))
+        return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: null pointer");
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: nunits and nlists are limited to 0x7FFFFFFF");
+    if (nlists && ws_bytes < tpf_p4nenc256v32_lists_workspace_size(nunits, nlists))
+        return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_enc(d_in, in_values, d_list_ptr, nlists, d1 != 0, d1 ? d_start0 : nullptr, d_out, out_cap, d_off,
+                                         nunits, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4nenc256v32_lists");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

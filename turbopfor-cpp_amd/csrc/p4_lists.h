@@ -1,6 +1,6 @@
-// p4_lists.h -- decode of many posting lists laid end to end in one call
-// (tpf_p4ndec256v32_lists, include/turbopfor_gpu.h): what the plan pass leaves
-// in the workspace for the kernels after it (internal).
+// p4_lists.h -- decode and encode of many posting lists laid end to end in one
+// call (tpf_p4ndec256v32_lists / tpf_p4nenc256v32_lists, include/turbopfor_gpu.h):
+// what the plan pass leaves in the workspace for the kernels after it (internal).
 //
 // Passes (p4_lists.hip): plan (one thread per list: unit
 // counts, structure check) -> run scan of the unit counts (p4_scan.h) -> heads
@@ -41,7 +41,23 @@ __device__ __forceinline__ bool lists_go(const ListsHdr * h, uint64_t nunits)
 namespace tpf
 {
 
+template <class T>
+struct RunScanWs; // p4_scan.h
+
 size_t lists_workspace(uint64_t nunits, uint64_t nlists);
+// The passes the decode and the encode (p4_lists_enc.hip) share: header reset,
+// plan, run scan of the lists' unit counts, heads.  `values`: the length of
+// the value array the pointers index (out_values / in_values).  `scan` covers
+// nlists entries, ubase nlists + 1, rec nunits.  A refused structure is
+// reported through `err`.
+hipError_t launch_lists_structure(const uint64_t * ptr, uint64_t nlists, uint64_t values, uint64_t nunits, dev::ListsHdr * hdr,
+                                  const RunScanWs<uint64_t> & scan, uint32_t * ubase, uint32_t * rec, unsigned long long * err,
+                                  hipStream_t s);
+// the many-lists encode (p4_lists_enc.hip)
+size_t lists_enc_workspace(uint64_t nunits, uint64_t nlists);
+hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint64_t * ptr, uint64_t nlists, bool d1,
+                            const uint32_t * start0, uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t nunits, void * ws,
+                            unsigned long long * err, hipStream_t s);
 hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                             uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
                             unsigned long long * err, hipStream_t s);

@@ -6,6 +6,7 @@
 #include "p4_lists.h"
 
 #include "p4_dec256v32.h"
+#include "p4_lists_dev.h"
 #include "p4_generic.h"
 #include "p4_scan.h"
 #include "tpf_kernels.h"
@@ -38,13 +39,6 @@ struct ListsArgs
     const uint32_t * run_tile;
     unsigned long long * err;
 };
-
-__device__ __forceinline__ uint32_t list_units(uint64_t n)
-{
-    // more units than any stream may hold: clamped, so the total cannot wrap back to nunits
-    const uint64_t u = (n >> 8) + ((n & 255u) != 0u ? 1u : 0u);
-    return u > 0x80000000ull ? 0x80000000u : static_cast<uint32_t>(u);
-}
 
 // Plan: one thread per list -- its unit count for the run scan and the
 // structure check -- and the unit records zeroed for the heads pass.
@@ -124,36 +118,6 @@ __global__ __launch_bounds__(256) void k_lists_pbase(uint64_t nlists, uint64_t n
             acc += sums[y];
         pbase[j] = acc;
     }
-}
-
-// Inclusive max-scan over the wave (identity 0).
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t x)
-{
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, false));
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, false));
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, false));
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, false));
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false));
-    x = umax32(x, __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false));
-    return x;
-}
-
-// The list holding unit `first`: the last j with ubase[j] <= first, by a
-// cooperative search -- 64 pivots per step, so 2^24 lists take 4 dependent
-// loads.  Invariant: ubase[lo] <= first < ubase[hi] (ubase[nlists] = nunits).
-__device__ __forceinline__ uint32_t find_list(const uint32_t * __restrict ubase, uint32_t nlists, uint32_t first, uint32_t t)
-{
-    uint32_t lo = 0u, hi = nlists;
-    while (hi - lo > 1u)
-    {
-        const uint32_t step = (hi - lo + 63u) / 64u;
-        const uint64_t p = static_cast<uint64_t>(lo) + static_cast<uint64_t>(t + 1u) * step;
-        const bool le = p < hi && ubase[p] <= first;
-        const uint32_t c = static_cast<uint32_t>(__builtin_popcountll(__ballot(le))); // ubase ascends: the first c pivots
-        lo = uni(lo + c * step);
-        hi = uni(umin32(hi, lo + step));
-    }
-    return lo;
 }
 
 // Decode of the full blocks: every wave owns a run of kRunDefault consecutive
@@ -395,6 +359,24 @@ uint32_t flat_grid(uint64_t items, hipStream_t s)
 
 size_t lists_workspace(uint64_t nunits, uint64_t nlists) { return ListsWs(nullptr, nunits, nlists).bytes; }
 
+hipError_t launch_lists_structure(const uint64_t * ptr, uint64_t nlists, uint64_t values, uint64_t nunits, dev::ListsHdr * hdr,
+                                  const RunScanWs<uint64_t> & scan, uint32_t * ubase, uint32_t * rec, unsigned long long * err,
+                                  hipStream_t s)
+{
+    hipError_t e = fill_u32(hdr, 0xFFFFFFFFu, 4, s);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_lists_plan, dim3(flat_grid(std::max(nunits, nlists), s)), dim3(256), 0, s, ptr, nlists, values, scan.tot,
+                       hdr, rec, nunits);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64(scan.tot, nlists, scan.pre, scan.tile, reinterpret_cast<uint64_t *>(&hdr->total), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_lists_heads, dim3(flat_grid(nlists, s)), dim3(256), 0, s, ptr, nlists, nunits, scan.pre, scan.tile, hdr,
+                       ubase, rec, err);
+    return hipGetLastError();
+}
+
 hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                             uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
                             unsigned long long * err, hipStream_t s)
@@ -404,19 +386,8 @@ hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_
     if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const ListsWs W(ws, nunits, nlists);
-    hipError_t e = fill_u32(W.hdr, 0xFFFFFFFFu, 4, s);
+    hipError_t e = launch_lists_structure(ptr, nlists, out_values, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
     if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(dev::k_lists_plan, dim3(flat_grid(std::max(nunits, nlists), s)), dim3(256), 0, s, ptr, nlists, out_values,
-                       W.scan.tot, W.hdr, W.rec, nunits);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    if ((e = launch_run_scan_u64(W.scan.tot, nlists, W.scan.pre, W.scan.tile, reinterpret_cast<uint64_t *>(&W.hdr->total), s))
-        != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(dev::k_lists_heads, dim3(flat_grid(nlists, s)), dim3(256), 0, s, ptr, nlists, nunits, W.scan.pre, W.scan.tile,
-                       W.hdr, W.ubase, W.rec, err);
-    if ((e = hipGetLastError()) != hipSuccess)
         return e;
     dev::ListsArgs A{in, in_bytes, off, nunits, ptr, nlists, start0, out, W.hdr, W.rec, W.ubase, W.pbase,
                      nullptr, nullptr, nullptr, err};

@@ -127,6 +127,15 @@ def lib():
             L.tpf_p4ndec256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp,
                                                  ctypes.c_size_t, c_vp, c_vp]
             L.tpf_p4ndec256v32_lists.restype = ctypes.c_int
+        # the many-lists encode: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_p4nenc256v32_lists"):
+            L.tpf_p4nenc256v32_lists_bound.argtypes = [c_u64, c_u64]
+            L.tpf_p4nenc256v32_lists_bound.restype = c_u64
+            L.tpf_p4nenc256v32_lists_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_p4nenc256v32_lists_workspace_size.restype = ctypes.c_size_t
+            L.tpf_p4nenc256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp, c_u64, c_vp,
+                                                 ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_p4nenc256v32_lists.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -506,3 +515,49 @@ def decn256v32_lists(packed, offsets, list_ptr, d1=False, start0=None, out=None,
     _check(L.tpf_p4ndec256v32_lists(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), nlists, int(bool(d1)),
                                     _ptr(start0), _ptr(out), out.numel(), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
+
+
+# ---- many lists in one call, encode (include/turbopfor_gpu.h tpf_p4nenc256v32_lists) ----
+def lists_enc_bound(nvalues, nlists):
+    """A capacity in bytes that always suffices for encn256v32_lists of
+    nvalues values in nlists lists (tpf_p4nenc256v32_lists_bound: advice, not a
+    precondition -- the device checks the real length against the capacity)."""
+    return int(lib().tpf_p4nenc256v32_lists_bound(int(nvalues), int(nlists)))
+
+
+def encn256v32_lists(values, list_ptr, d1=False, start0=None, nunits=None, out=None, offsets=None, err=None, ws=None):
+    """Encode many lists laid end to end in one call: list j is
+    values[list_ptr[j]:list_ptr[j+1]] and becomes an encn256v32-layout stream,
+    the streams concatenated in list order -- what decn256v32_lists reads.
+    values: int32 CUDA tensor (its numel() is the readable length); list_ptr:
+    int64 CUDA tensor [nlists + 1] (CSR form); start0: optional int32 CUDA
+    tensor [nlists] of each list's preceding value (d1 only; None = 0).
+    nunits: the stream's unit count (default: computed from list_ptr with
+    lists_units, which costs a device-to-host read).  out: uint8 CUDA tensor
+    whose numel() is the capacity (default: lists_enc_bound bytes, trimmed to
+    offsets[-1], which costs another read); offsets: int64 CUDA tensor
+    [nunits + 1]; err: optional int64 CUDA tensor [1] (-1 = clean).  With
+    nunits, out and offsets all given the call stays asynchronous and returns
+    out untrimmed.  Returns (packed, offsets)."""
+    import torch
+
+    assert values.is_cuda and values.dtype == torch.int32
+    values = values.contiguous().view(-1)
+    nlists = list_ptr.numel() - 1
+    if nunits is None:
+        nunits = int(lists_units(list_ptr)[1][-1])
+    trim = out is None
+    if out is None:
+        nvalues = int(list_ptr[-1].item()) - int(list_ptr[0].item()) if nlists > 0 else 0
+        out = torch.empty(max(lists_enc_bound(nvalues, nlists), 1), dtype=torch.uint8, device=values.device)
+    if offsets is None:
+        offsets = torch.empty(nunits + 1, dtype=torch.int64, device=values.device)
+    L = lib()
+    ws_bytes = int(L.tpf_p4nenc256v32_lists_workspace_size(nunits, nlists))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=values.device)
+    _check(L.tpf_p4nenc256v32_lists(_ptr(values), values.numel(), _ptr(list_ptr), nlists, int(bool(d1)), _ptr(start0), _ptr(out),
+                                    out.numel(), _ptr(offsets), nunits, _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    if trim:
+        out = out[:int(offsets[nunits].item())]
+    return out, offsets
