@@ -285,6 +285,85 @@ int tpf_p4nenc256v32_lists(const uint32_t *d_in, uint64_t in_values, const uint6
                            const uint32_t *d_start0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_off, uint64_t nunits,
                            void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- the read side of a resident index ---------------------------------------
+ * A search engine keeps the stream of tpf_p4nenc256v32_lists resident and, for
+ * each batch of queries, decodes the few lists the query terms name.
+ *
+ * tpf_lists_unit_base builds the UNIT DIRECTORY of a stream, once per index,
+ * to be kept beside d_off and d_list_ptr: d_list_unit[j] is the index of the
+ * first unit of list j -- the exclusive prefix sum of units_j = n_j/256 +
+ * (n_j%256 != 0) -- and d_list_unit[nlists] the unit count of the stream.
+ *   - Errors through d_err (optional; UINT64_MAX = clean): the first list j
+ *     with ptr[j+1] < ptr[j] is reported as j, a unit total above 0x7FFFFFFF as
+ *     nlists; in both cases nothing is written to d_list_unit.
+ *   - TPF_EINVAL: a null d_list_unit; a null d_list_ptr or d_ws, or ws_bytes
+ *     below tpf_lists_unit_base_workspace_size(nlists), when nlists is
+ *     non-zero; nlists above 0x7FFFFFFF.  nlists == 0 writes d_list_unit[0] = 0.
+ *   - Everything is enqueued on `stream`. */
+size_t tpf_lists_unit_base_workspace_size(uint64_t nlists);
+int tpf_lists_unit_base(const uint64_t *d_list_ptr, uint64_t nlists, uint32_t *d_list_unit /* nlists + 1 */, void *d_ws,
+                        size_t ws_bytes, uint64_t *d_err, void *stream);
+
+/* tpf_p4ndec256v32_lists_select decodes lists d_sel[0..nsel) of a resident
+ * stream, in the order given, into one dense output, in ONE submission whose
+ * cost depends on what is selected and not on the size of the index.
+ *   - Output layout: selection k names list j = d_sel[k] of n_j = ptr[j+1] -
+ *     ptr[j] values, written to d_out + d_out_ptr[k]; d_out_ptr[0] = 0 and
+ *     d_out_ptr[k+1] = d_out_ptr[k] + n_j, so the output is dense, in selection
+ *     order, and itself a CSR array (d_out_ptr: nsel + 1 entries, written).
+ *     Only differences of d_list_ptr are used: its absolute values need not
+ *     fit out_values.  The same list may be selected several times, each
+ *     occurrence getting its own copy; empty lists may be selected, any number
+ *     in a row.
+ *   - Source units: the units of list j are d_list_unit[j] .. d_list_unit[j+1]
+ *     of the stream (tpf_lists_unit_base), under the OFFSETS CONTRACT above.
+ *   - Delta-1: with d1 != 0 the first unit of selection k starts from
+ *     d_start0[d_sel[k]] -- d_start0 is indexed by the lists of the INDEX;
+ *     NULL means 0 -- and every later unit, the tail included, from the
+ *     decoded value before it, mod 2^32.  The results are exactly those of
+ *     tpf_p4ndec256v32_lists.  With d1 == 0 d_start0 is ignored.
+ *   - Output bounds: nothing is written at or past d_out + out_values, and
+ *     nothing outside [d_out_ptr[k], d_out_ptr[k+1]) for any k.  d_out is only
+ *     4-byte aligned.
+ *   - Cost: no kernel is sized by nlists or nunits, and no pass reads d_off,
+ *     d_in, d_list_ptr, d_list_unit or d_start0 at a list or unit that is not
+ *     selected -- but for d_list_ptr[j+1], d_list_unit[j+1] and the end offset
+ *     of a selected list's last unit.  Grids and the workspace are sized on
+ *     the host from nsel and out_values alone: a selection that fits holds at
+ *     most out_values/256 + nsel units (waves past the real count exit), so
+ *     pass the capacity the selection needs, not the index's.  The number of
+ *     launches is fixed, whatever the selection.  With d1 every selected full
+ *     block is decoded twice (once for its sum, once for its values).
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       < nunits        the SOURCE unit index of the first selected unit whose
+ *                       parse disagrees with its offsets (the lowest such
+ *                       index when several disagree);
+ *       nunits + k      the first selection k with d_sel[k] >= nlists,
+ *                       ptr[j+1] < ptr[j], d_list_unit[j+1] - d_list_unit[j]
+ *                       different from the unit count of n_j, or
+ *                       d_list_unit[j+1] > nunits: nothing is written to d_out
+ *                       or d_out_ptr;
+ *       nunits + nsel   the selected values do not fit out_values: nothing is
+ *                       written to d_out, but d_out_ptr is filled completely,
+ *                       so d_out_ptr[nsel] tells the caller what to allocate
+ *                       (the rule tpf_p4nenc256v32_lists uses for out_cap).
+ *   - TPF_EINVAL (decided before any device call): with nsel non-zero a null
+ *     d_sel, d_out_ptr, d_in, d_off, d_list_ptr, d_list_unit, d_out or d_ws, or
+ *     ws_bytes below tpf_p4ndec256v32_lists_select_workspace_size(nsel,
+ *     out_values); nlists, nunits, nsel or out_values/256 + nsel above
+ *     0x7FFFFFFF.  nsel == 0 is a successful no-op that writes d_out_ptr[0] = 0
+ *     and sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_p4ndec256v32_lists_select_workspace_size(uint64_t nsel, uint64_t out_values);
+int tpf_p4ndec256v32_lists_select(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                                  const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists, int d1,
+                                  const uint32_t *d_start0, const uint32_t *d_sel, uint64_t nsel, uint32_t *d_out,
+                                  uint64_t out_values, uint64_t *d_out_ptr /* nsel + 1 */, void *d_ws, size_t ws_bytes,
+                                  uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

@@ -531,6 +531,56 @@ int tpf_p4nenc256v32_lists(const uint32_t * d_in, uint64_t in_values, const uint
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4nenc256v32_lists");
 }
 
+// ---- the read side of a resident index: the unit directory and the decode of
+// a selection of lists.  Arguments are judged before the device is looked for.
+size_t tpf_lists_unit_base_workspace_size(uint64_t nlists) { return tpf::lists_unit_base_workspace(nlists); }
+
+int tpf_lists_unit_base(const uint64_t * d_list_ptr, uint64_t nlists, uint32_t * d_list_unit, void * d_ws, size_t ws_bytes, uint64_t * d_err,
+                        void * stream)
+{
+    if (nlists > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_unit_base: nlists is limited to 0x7FFFFFFF");
+    if (!d_list_unit || (nlists && (!d_list_ptr || !d_ws)))
+        return fail(TPF_EINVAL, "tpf_lists_unit_base: null pointer");
+    if (nlists && ws_bytes < tpf_lists_unit_base_workspace_size(nlists))
+        return fail(TPF_EINVAL, "tpf_lists_unit_base: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_unit_base(d_list_ptr, nlists, d_list_unit, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_unit_base");
+}
+
+size_t tpf_p4ndec256v32_lists_select_workspace_size(uint64_t nsel, uint64_t out_values)
+{
+    return tpf::lists_select_workspace(nsel, out_values);
+}
+
+int tpf_p4ndec256v32_lists_select(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits,
+                                  const uint64_t * d_list_ptr, const uint32_t * d_list_unit, uint64_t nlists, int d1,
+                                  const uint32_t * d_start0, const uint32_t * d_sel, uint64_t nsel, uint32_t * d_out, uint64_t out_values,
+                                  uint64_t * d_out_ptr, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nsel > 0x7FFFFFFFull
+        || (nsel && tpf::lists_select_unit_cap(nsel, out_values) > 0x7FFFFFFFull))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: nlists, nunits, nsel and out_values / 256 + nsel are limited to 0x7FFFFFFF");
+    if (nsel && (!d_sel || !d_out_ptr || !d_in || !d_off || !d_list_ptr || !d_list_unit || !d_out || !d_ws))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: null pointer");
+    if (nsel && ws_bytes < tpf_p4ndec256v32_lists_select_workspace_size(nsel, out_values))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_select(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
+                                            d1 ? d_start0 : nullptr, d_sel, nsel, d_out, out_values, d_out_ptr, d_ws,
+                                            reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_select");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

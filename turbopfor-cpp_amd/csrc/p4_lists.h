@@ -61,6 +61,22 @@ hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint6
 hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                             uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
                             unsigned long long * err, hipStream_t s);
+// the read side of a resident index (p4_lists_select.hip): the
+// unit directory of a stream, and the decode of a selection of its lists.
+// Passes of the selective decode: plan over the SELECTION -> two run scans
+// (virtual unit bases, d_out_ptr) -> heads (records of the virtual units) ->
+// [delta-1: block sums of the virtual units, their run scan, one prefix per
+// selection] -> full blocks -> tails.  vcap = lists_select_unit_cap: the most
+// units a selection that fits out_values can hold; it sizes grids and workspace.
+size_t lists_unit_base_workspace(uint64_t nlists);
+hipError_t launch_lists_unit_base(const uint64_t * ptr, uint64_t nlists, uint32_t * list_unit, void * ws, unsigned long long * err,
+                                  hipStream_t s);
+uint64_t lists_select_unit_cap(uint64_t nsel, uint64_t out_values);
+size_t lists_select_workspace(uint64_t nsel, uint64_t out_values);
+hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
+                               uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
+                               hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

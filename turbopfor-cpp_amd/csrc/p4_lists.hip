@@ -14,12 +14,6 @@
 namespace tpf::dev
 {
 
-constexpr uint32_t kListSlot = 2432;      // k_lists_tails: the generic decoder's slot (a 2,304-byte image + 128)
-constexpr uint32_t kListScratchU32 = 512; // decode_block_g<H32>'s scratch
-constexpr uint32_t kListsNC = 6;          // k_lists_dec: the k_dec256v32w pipeline, 7 waves per SIMD
-constexpr int kListsMinW = 7;
-constexpr uint32_t kTailsNC = 4;          // k_lists_tails: the k_dec_gr pipeline
-
 struct ListsArgs
 {
     const uint8_t * in;

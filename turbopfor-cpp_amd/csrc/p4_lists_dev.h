@@ -1,5 +1,6 @@
 // p4_lists_dev.h -- device helpers shared by the many-lists decode
-// (p4_lists.hip) and encode (p4_lists_enc.hip): a list's unit count, and how
+// (p4_lists.hip), its selective form (p4_lists_select.hip) and the many-lists
+// encode (p4_lists_enc.hip): the pipeline shapes, a list's unit count, and how
 // every lane of a wave's run of units finds its list from the unit records
 // (p4_lists.h).  Device code only: included by *.hip files (internal).
 #pragma once
@@ -9,6 +10,13 @@
 
 namespace tpf::dev
 {
+
+// pipeline shapes of the lists decodes (p4_lists.hip, p4_lists_select.hip)
+constexpr uint32_t kListSlot = 2432;      // tails: the generic decoder's slot (a 2,304-byte image + 128)
+constexpr uint32_t kListScratchU32 = 512; // decode_block_g<H32>'s scratch
+constexpr uint32_t kListsNC = 6;          // full blocks: the k_dec256v32w pipeline, 7 waves per SIMD
+constexpr int kListsMinW = 7;
+constexpr uint32_t kTailsNC = 4;          // tails: the k_dec_gr pipeline
 
 __device__ __forceinline__ uint32_t list_units(uint64_t n)
 {

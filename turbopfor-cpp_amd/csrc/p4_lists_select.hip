@@ -1,0 +1,588 @@
+// p4_lists_select.hip -- the read side of a resident index (p4_lists.h,
+// DESIGN.md 4.9): tpf_lists_unit_base builds the unit directory of a lists
+// stream once, tpf_p4ndec256v32_lists_select decodes lists sel[0 .. nsel) of
+// it, in the order given, into one dense output.  The selection takes the
+// role the index's lists play in p4_lists.hip: the selected lists' units,
+// laid end to end in selection order, are the VIRTUAL unit sequence every pass
+// after the plan works on; virtual unit v of selection k is source unit
+// list_unit[sel[k]] + (v - vbase[k]) of the stream.  No pass is sized by the
+// index, and none reads it at a list or unit that is not selected.
+#include "p4_lists.h"
+
+#include "p4_dec256v32.h"
+#include "p4_lists_dev.h"
+#include "p4_generic.h"
+#include "p4_scan.h"
+#include "tpf_kernels.h"
+
+namespace tpf::dev
+{
+
+struct SelHdr
+{
+    unsigned long long bad;    // first refused selection k (~0: none)
+    unsigned long long vtotal; // virtual units: the sum of the selections' unit counts
+    unsigned long long ototal; // selected values: d_out_ptr[nsel]
+};
+
+// go / no-go: every selection is sound and the selected values fit the output
+// (then vtotal <= vcap follows, a list of n values holding at most n/256 + 1
+// units; it is checked all the same: vcap sizes the records and the sums)
+__device__ __forceinline__ bool sel_go(const SelHdr * h, uint64_t out_values, uint64_t vcap)
+{
+    return h->bad == ~0ull && h->ototal <= out_values && h->vtotal <= vcap;
+}
+
+struct SelArgs
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    const uint32_t * list_unit;
+    const uint32_t * start0;
+    const uint32_t * sel;
+    uint64_t nsel;
+    uint32_t * out;
+    uint64_t out_values;
+    uint64_t vcap;             // the host's cap on the virtual units: out_values / 256 + nsel
+    const uint64_t * out_ptr;  // d_out_ptr (written by the heads pass)
+    const SelHdr * hdr;
+    const uint32_t * rec;      // records of the virtual units (p4_lists.h)
+    const uint32_t * vbase;    // first virtual unit of every selection, nsel + 1
+    const uint32_t * pbase;    // delta-1: prefix of the block sums at vbase[k], k <= nsel
+    uint32_t * sums;           // delta-1: block sums of the virtual units (tails 0)
+    uint32_t * run_tot;        // delta-1: one total per 16-unit decode run
+    const uint32_t * run_pre;
+    const uint32_t * run_tile;
+    unsigned long long * err;
+};
+
+// ---- the unit directory ---------------------------------------------------
+__global__ __launch_bounds__(256) void k_unit_base_plan(const uint64_t * __restrict ptr, uint64_t nlists, uint32_t * __restrict tot,
+                                                         unsigned long long * __restrict bad)
+{
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; j < nlists; j += gsz)
+    {
+        const uint64_t a = ptr[j], b = ptr[j + 1u];
+        tot[j] = b < a ? 0u : list_units(b - a);
+        if (b < a)
+            atomicMin(bad, static_cast<unsigned long long>(j));
+    }
+}
+
+// hdr[0]: first decreasing pointer, hdr[1]: the unit total
+__global__ __launch_bounds__(256) void k_unit_base_write(uint64_t nlists, const uint64_t * __restrict pre, const uint64_t * __restrict tile,
+                                                          const unsigned long long * __restrict hdr, uint32_t * __restrict list_unit,
+                                                          unsigned long long * __restrict err)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const unsigned long long bad = hdr[0], total = hdr[1];
+    if (bad != ~0ull || total > 0x7FFFFFFFull)
+    {
+        if (gid == 0 && err != nullptr)
+            *err = bad != ~0ull ? bad : nlists;
+        return;
+    }
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t j = gid; j < nlists; j += gsz)
+        list_unit[j] = static_cast<uint32_t>(run_base(pre, tile, j));
+    if (gid == 0)
+        list_unit[nlists] = static_cast<uint32_t>(total);
+}
+
+// ---- the selective decode ---------------------------------------------------
+// Plan: one thread per SELECTION -- its list's unit and value counts for the
+// two run scans, and the checks of everything the later passes index with
+// (the values are checked here, never followed) -- and the records of the
+// virtual units zeroed for the heads pass, up to the host's cap.
+__global__ __launch_bounds__(256) void k_sel_plan(const uint64_t * __restrict ptr, const uint32_t * __restrict list_unit, uint64_t nlists,
+                                                   uint64_t nunits, const uint32_t * __restrict sel, uint64_t nsel,
+                                                   uint32_t * __restrict totu, uint64_t * __restrict totv, SelHdr * __restrict hdr,
+                                                   uint32_t * __restrict rec, uint64_t vcap)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t k = gid; k < nsel; k += gsz)
+    {
+        const uint32_t j = sel[k];
+        bool bad = j >= nlists;
+        uint64_t n = 0u;
+        uint32_t units = 0u;
+        if (!bad)
+        {
+            const uint64_t a = ptr[j], b = ptr[j + 1u];
+            const uint32_t ua = list_unit[j], ub = list_unit[j + 1u];
+            bad = b < a || ub < ua || ub > nunits;
+            if (!bad)
+            {
+                n = b - a;
+                units = list_units(n);
+                bad = ub - ua != units;
+            }
+        }
+        totu[k] = bad ? 0u : units;
+        totv[k] = bad ? 0ull : n;
+        if (bad)
+            atomicMin(&hdr->bad, static_cast<unsigned long long>(k));
+    }
+    for (uint64_t u = gid; u < vcap; u += gsz)
+        rec[u] = 0u;
+}
+
+// Heads: the verdict (d_err for a refused selection or an output that is too
+// small), d_out_ptr, then per selection its virtual unit base and the records
+// of its first unit and of its tail -- the head carries k + 1, the SELECTION.
+__global__ __launch_bounds__(256) void k_sel_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap,
+                                                    const uint32_t * __restrict totu, const uint64_t * __restrict totv,
+                                                    const uint64_t * __restrict preu, const uint64_t * __restrict tileu,
+                                                    const uint64_t * __restrict prev, const uint64_t * __restrict tilev,
+                                                    const SelHdr * __restrict hdr, uint32_t * __restrict vbase, uint32_t * __restrict rec,
+                                                    uint64_t * __restrict out_ptr, unsigned long long * __restrict err)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    if (hdr->bad != ~0ull)
+    {
+        if (gid == 0 && err != nullptr)
+            *err = nunits + hdr->bad;
+        return;
+    }
+    const bool go = sel_go(hdr, out_values, vcap);
+    for (uint64_t k = gid; k < nsel; k += gsz)
+        out_ptr[k] = run_base(prev, tilev, k);
+    if (gid == 0)
+    {
+        out_ptr[nsel] = hdr->ototal;
+        if (!go && err != nullptr)
+            *err = nunits + nsel;
+    }
+    if (!go)
+        return;
+    for (uint64_t k = gid; k < nsel; k += gsz)
+    {
+        const uint32_t vb = static_cast<uint32_t>(run_base(preu, tileu, k)); // <= vtotal <= vcap < 2^31
+        vbase[k] = vb;
+        const uint32_t units = totu[k];
+        const bool tail = (totv[k] & 255u) != 0u;
+        if (units == 1u)
+            rec[vb] = static_cast<uint32_t>(k + 1u) | (tail ? kRecTail : 0u);
+        else if (units != 0u)
+        {
+            rec[vb] = static_cast<uint32_t>(k + 1u);
+            if (tail)
+                rec[vb + units - 1u] = kRecTail;
+        }
+    }
+    if (gid == 0)
+        vbase[nsel] = static_cast<uint32_t>(hdr->vtotal);
+}
+
+// Delta-1: pbase[k] = P(vbase[k]) for k = 0 .. nsel, P(x) = the sum of every
+// block sum before virtual unit x (mod 2^32; vbase[nsel] = vtotal): the base of
+// the 16-unit run of the sums pass plus at most 16 sums.
+__global__ __launch_bounds__(256) void k_sel_pbase(const SelArgs A, uint32_t * __restrict pbase)
+{
+    if (!sel_go(A.hdr, A.out_values, A.vcap))
+        return;
+    const uint64_t vt = A.hdr->vtotal;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; k <= A.nsel; k += gsz)
+    {
+        uint32_t acc = 0u;
+        if (vt != 0u)
+        {
+            const uint32_t x = A.vbase[k];
+            const uint32_t y = x < vt ? x : static_cast<uint32_t>(vt - 1u); // the last run exists; P(vtotal) = P(vtotal-1) + its sum
+            acc = run_base(A.run_pre, A.run_tile, y / kRunDefault);
+            for (uint32_t q = y / kRunDefault * kRunDefault; q < y; ++q)
+                acc += A.sums[q];
+            if (x >= vt)
+                acc += A.sums[y];
+        }
+        pbase[k] = acc;
+    }
+}
+
+// Full blocks: every wave owns a run of kRunDefault consecutive VIRTUAL units
+// with the k_dec256v32w pipeline, as k_lists_dec does for the units of a
+// stream.  Lane t resolves the selection k of virtual unit first + t from the
+// head records inside the run and one search over vbase for the run's first
+// unit, then gathers sel[k] and list_unit[sel[k]] and loads the offsets of its
+// SOURCE unit; the blocks of a run lie anywhere in the stream, which the run
+// plane never assumed otherwise.  The output of a run is still one contiguous
+// range (the output is dense in selection order): one buffer descriptor.
+// SUM (delta-1's first pass): the same decode, but every block's sum of
+// (v + 1) goes to sums[] and the run's total to run_tot[] instead of the
+// values to the output.  (The lists decode sums a contiguous stream through
+// LDS windows of 16 KB, k_dsum256v32_lists; scattered source units have no
+// such windows, so this pass pays a full decode per block.)
+template <bool D1, uint32_t NC, int MINW, bool SUM>
+__global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
+{
+    __shared__ uint32_t slots[4][kSlotBytes / 4];
+    __shared__ uint32_t scratch[4][kWaveScratchU32];
+    // the run's source units, for the error report only: held in a register
+    // across the pipeline they cost the delta-1 form 6 spilled VGPRs at 7 waves
+    __shared__ uint32_t srcu[4][kRunDefault];
+    if (!sel_go(A.hdr, A.out_values, A.vcap))
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    uint32_t * scr = scratch[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t vt = A.hdr->vtotal;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= vt)
+    {
+        // the grid is sized by the host's cap: a wave past the real count has
+        // nothing to do but leave its run total defined for the scan
+        if (SUM && t == 0 && first < A.vcap)
+            A.run_tot[first / kRun] = 0u;
+        return;
+    }
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, vt - first));
+    const bool valid = t < n;
+    const uint64_t v = first + t;
+    const uint32_t r = valid ? A.rec[v] : 0u;
+    const bool full = valid && (r & kRecTail) == 0u;
+    const uint64_t fullmask = __ballot(full);
+    if (fullmask == 0ull)
+    {
+        if constexpr (SUM)
+        {
+            if (valid)
+                A.sums[v] = 0u;
+            if (t == 0)
+                A.run_tot[first / kRun] = 0u;
+        }
+        return; // a run of tails only
+    }
+
+    // ---- the selection of every unit: heads inside the run, the search before it
+    const uint32_t r0 = rl(r, 0) & kRecList;
+    const uint32_t k0 = r0 != 0u ? r0 - 1u : find_list(A.vbase, static_cast<uint32_t>(A.nsel), static_cast<uint32_t>(first), t);
+    const uint32_t id = umax32(wave_incl_max(r & kRecList), k0 + 1u) - 1u;
+    const uint32_t vb = valid ? A.vbase[id] : 0u;
+    const uint32_t lj = valid ? A.sel[id] : 0u;
+    const uint32_t inl = static_cast<uint32_t>(v) - vb; // unit v - vb of its list
+    // the source unit: the plan checked sel[k] < nlists and list_unit[j] + units_j <= nunits
+    const uint32_t su = full ? A.list_unit[lj] + inl : 0u;
+    const uint64_t o = full ? A.off[su] : 0ull;
+    const uint64_t e = full ? A.off[su + 1u] : 0ull;
+    RunPlaneT<kSlotBytes, true> P;
+    P.init(in_base, in_end, o, e, full);
+    if (!SUM && t < kRun)
+        srcu[wv][t] = full ? su : 0xFFFFFFFFu;
+
+    // (the output plane's gathers depend on the selection only, like the
+    // offsets': they are settled before the chunks go in flight, which keeps
+    // the delta-1 form inside the registers of 7 waves per SIMD)
+    uint32_t rel = 0u, startv = 0u, sumv = 0u;
+    __amdgpu_buffer_rsrc_t ors = make_rsrc(A.out, 0u);
+    if constexpr (!SUM)
+    {
+        const uint64_t opos = (valid ? A.out_ptr[id] : 0ull) + 256ull * inl;
+        const uint64_t opos0 = readlane_u64(opos, 0);
+        rel = static_cast<uint32_t>(opos - opos0) * 4u; // bytes from the run's first value
+        const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
+        ors = make_rsrc(A.out + opos0, rl(rel, lastf) + 1024u);
+        if constexpr (D1)
+        {
+            // start0[list] + P(v) - P(vbase[k]) mod 2^32, P = the prefix of the
+            // block sums over the virtual units (tails count 0)
+            const uint32_t sv = valid ? A.sums[v] : 0u;
+            const uint32_t pu = run_base(A.run_pre, A.run_tile, first / kRun) + wave_incl_scan(sv) - sv;
+            const uint32_t s0 = (valid && A.start0 != nullptr) ? A.start0[lj] : 0u;
+            startv = valid ? s0 + pu - A.pbase[id] : 0u;
+        }
+    }
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((fullmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        u32x4 x;
+        const uint32_t used = decode_block256v32(slot, (ctl >> kCtlShift) & 15u, P.head(c, ctl, slot), scr, t, x);
+        if constexpr (SUM)
+        {
+            const uint32_t sm = wave_sum(x.x + x.y + x.z + x.w + 4u);
+            sumv = t == jj ? sm : sumv;
+        }
+        else
+        {
+            if constexpr (D1)
+                apply_delta1_256(x, rl(startv, jj));
+            st16_run(ors, rl(rel, jj) + 16u * t, x);
+        }
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+
+    bool more = true;
+    for (uint32_t j = 0; more; j += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], j + q + NC - 1, t);
+                consume(C[q], j + q);
+                more = j + q + 1 < n;
+            }
+        }
+    }
+    if constexpr (SUM)
+    {
+        // the decode pass re-checks every unit: parse errors are reported there
+        sumv = full ? sumv : 0u;
+        if (valid)
+            A.sums[v] = sumv;
+        publish_run_total(A.run_tot, first / kRun, sumv, t);
+    }
+    else if (A.err != nullptr && badmask != 0u)
+    {
+        // in stream numbering; the source units of a run do not ascend
+        const uint32_t m = wave_min((t < kRun && ((badmask >> t) & 1ull) != 0ull) ? srcu[wv][t] : 0xFFFFFFFFu);
+        if (t == 0)
+            atomicMin(A.err, static_cast<unsigned long long>(m));
+    }
+}
+
+// Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
+// decoder's pipeline, as k_lists_tails does for the lists of a stream; lane t
+// holds selection first + t's tail unit -- source unit list_unit[sel[k]] +
+// n / 256 of n % 256 values at the end of the selection's output -- or
+// nothing.  Delta-1: the tail starts at start0 + P(vbase[k + 1]) - P(vbase[k]).
+// (A kernel of its own for the reason recorded above k_lists_tails.)
+template <bool D1, uint32_t NC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sel_tails(const SelArgs A)
+{
+    __shared__ uint32_t slots[4][kListSlot / 4];
+    __shared__ uint32_t scratch[4][kListScratchU32];
+    if (!sel_go(A.hdr, A.out_values, A.vcap))
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= A.nsel)
+        return;
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nsel - first));
+    const uint64_t k = first + t;
+    const uint64_t p0 = t < n ? A.out_ptr[k] : 0ull;
+    const uint64_t p1 = t < n ? A.out_ptr[k + 1u] : 0ull;
+    const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
+    const bool has = cnt != 0u;
+    const uint64_t hasmask = __ballot(has);
+    if (hasmask == 0ull)
+        return;
+    const uint32_t lj = has ? A.sel[k] : 0u;
+    const uint32_t su = has ? A.list_unit[lj] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
+    const uint64_t o = has ? A.off[su] : 0ull;
+    const uint64_t e = has ? A.off[su + 1u] : 0ull;
+    RunPlaneT<kListSlot> P;
+    P.init(in_base, in_end, o, e, has);
+    const uint64_t opos = p1 - cnt;
+    uint32_t startv = 0u;
+    if constexpr (D1)
+        startv = has ? (A.start0 != nullptr ? A.start0[lj] : 0u) + A.pbase[k + 1u] - A.pbase[k] : 0u;
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((hasmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        const uint32_t cj = rl(cnt, jj);
+        uint32_t x[4], cm;
+        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
+        if constexpr (D1)
+            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        uint32_t * op = A.out + readlane_u64(opos, jj);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+            if (t + 64u * q < cj)
+                __builtin_nontemporal_store(x[q], op + t + 64u * q);
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+    bool more = true;
+    for (uint32_t jb = 0; more; jb += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
+                consume(C[q], jb + q);
+                more = jb + q + 1 < n;
+            }
+        }
+    }
+    if (A.err != nullptr && badmask != 0u)
+    {
+        const uint32_t m = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
+        if (t == 0)
+            atomicMin(A.err, static_cast<unsigned long long>(m));
+    }
+}
+
+} // namespace tpf::dev
+
+namespace tpf
+{
+
+namespace
+{
+size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
+
+uint64_t sel_runs(uint64_t vcap) { return (vcap + dev::kRunDefault - 1u) / dev::kRunDefault; }
+
+// Workspace of the selective decode: header | run scan of the selections'
+// unit counts | their value counts and that scan (u64) | vbase (nsel + 1) |
+// pbase (nsel + 1) | records of the virtual units (vcap) | block sums (vcap)
+// and the scan of their 16-unit run totals, each 256-byte aligned.
+struct SelWs
+{
+    dev::SelHdr * hdr;
+    RunScanWs<uint64_t> scanu;
+    uint64_t *totv, *prev, *tilev;
+    uint32_t *vbase, *pbase, *rec, *sums;
+    RunScanWs<uint32_t> scans;
+    size_t bytes;
+
+    SelWs(void * ws, uint64_t nsel, uint64_t vcap)
+    {
+        auto * p = static_cast<uint8_t *>(ws);
+        size_t x = 0;
+        hdr = reinterpret_cast<dev::SelHdr *>(p + x);
+        x += 256u;
+        scanu = RunScanWs<uint64_t>::carve(p + x, nsel);
+        x += al256(RunScanWs<uint64_t>::bytes(nsel));
+        totv = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * nsel);
+        prev = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * nsel);
+        tilev = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * RunScanWs<uint64_t>::tiles(nsel)) + 256u;
+        vbase = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * (nsel + 1u));
+        pbase = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * (nsel + 1u));
+        rec = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * vcap);
+        sums = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * vcap);
+        scans = RunScanWs<uint32_t>::carve(p + x, sel_runs(vcap));
+        x += al256(RunScanWs<uint32_t>::bytes(sel_runs(vcap)));
+        bytes = x;
+    }
+};
+
+uint32_t flat_grid(uint64_t items, hipStream_t s)
+{
+    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
+}
+} // namespace
+
+size_t lists_unit_base_workspace(uint64_t nlists) { return 256u + al256(RunScanWs<uint64_t>::bytes(nlists)); }
+
+hipError_t launch_lists_unit_base(const uint64_t * ptr, uint64_t nlists, uint32_t * list_unit, void * ws, unsigned long long * err,
+                                  hipStream_t s)
+{
+    if (nlists == 0)
+        return fill_u32(list_unit, 0u, 1, s);
+    auto * hdr = static_cast<unsigned long long *>(ws);
+    const RunScanWs<uint64_t> scan = RunScanWs<uint64_t>::carve(static_cast<uint8_t *>(ws) + 256u, nlists);
+    hipError_t e = fill_u32(hdr, 0xFFFFFFFFu, 4, s);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_unit_base_plan, dim3(flat_grid(nlists, s)), dim3(256), 0, s, ptr, nlists, scan.tot, hdr);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64(scan.tot, nlists, scan.pre, scan.tile, reinterpret_cast<uint64_t *>(hdr + 1), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_unit_base_write, dim3(flat_grid(nlists, s)), dim3(256), 0, s, nlists, scan.pre, scan.tile, hdr, list_unit, err);
+    return hipGetLastError();
+}
+
+uint64_t lists_select_unit_cap(uint64_t nsel, uint64_t out_values) { return out_values / 256u + nsel; }
+
+size_t lists_select_workspace(uint64_t nsel, uint64_t out_values)
+{
+    return SelWs(nullptr, nsel, lists_select_unit_cap(nsel, out_values)).bytes;
+}
+
+hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
+                               uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
+                               hipStream_t s)
+{
+    if (nsel == 0)
+        return out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess;
+    const uint64_t vcap = lists_select_unit_cap(nsel, out_values);
+    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    const SelWs W(ws, nsel, vcap);
+    hipError_t e = fill_u32(W.hdr, 0xFFFFFFFFu, 2, s);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_sel_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, nsel,
+                       W.scanu.tot, W.totv, W.hdr, W.rec, vcap);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64(W.scanu.tot, nsel, W.scanu.pre, W.scanu.tile, reinterpret_cast<uint64_t *>(&W.hdr->vtotal), s)) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64t(W.totv, nsel, W.prev, W.tilev, reinterpret_cast<uint64_t *>(&W.hdr->ototal), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_sel_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, W.scanu.tot, W.totv,
+                       W.scanu.pre, W.scanu.tile, W.prev, W.tilev, W.hdr, W.vbase, W.rec, out_ptr, err);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    const dev::SelArgs A{in, in_bytes, off, list_unit, start0, sel, nsel, out, out_values, vcap, out_ptr, W.hdr, W.rec, W.vbase, W.pbase,
+                         W.sums, W.scans.tot, W.scans.pre, W.scans.tile, err};
+    // sized by the host's cap: waves past the real unit count exit
+    const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    const uint32_t tgrid = static_cast<uint32_t>((nsel + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    if (!d1)
+    {
+        hipLaunchKernelGGL((dev::k_sel_dec<false, dev::kListsNC, dev::kListsMinW, false>), dim3(grid), dim3(256), 0, s, A);
+        if ((e = hipGetLastError()) != hipSuccess)
+            return e;
+        hipLaunchKernelGGL((dev::k_sel_tails<false, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((dev::k_sel_dec<false, dev::kListsNC, dev::kListsMinW, true>), dim3(grid), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u32(W.scans.tot, sel_runs(vcap), W.scans.pre, W.scans.tile, nullptr, s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_sel_pbase, dim3(flat_grid(nsel + 1u, s)), dim3(256), 0, s, A, W.pbase);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((dev::k_sel_dec<true, dev::kListsNC, dev::kListsMinW, false>), dim3(grid), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((dev::k_sel_tails<true, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+} // namespace tpf

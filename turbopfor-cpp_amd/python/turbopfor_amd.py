@@ -136,6 +136,17 @@ def lib():
             L.tpf_p4nenc256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp, c_u64, c_vp,
                                                  ctypes.c_size_t, c_vp, c_vp]
             L.tpf_p4nenc256v32_lists.restype = ctypes.c_int
+        # the unit directory and the selective decode: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_p4ndec256v32_lists_select"):
+            L.tpf_lists_unit_base_workspace_size.argtypes = [c_u64]
+            L.tpf_lists_unit_base_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_unit_base.argtypes = [c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_unit_base.restype = ctypes.c_int
+            L.tpf_p4ndec256v32_lists_select_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_p4ndec256v32_lists_select_workspace_size.restype = ctypes.c_size_t
+            L.tpf_p4ndec256v32_lists_select.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64,
+                                                        c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_p4ndec256v32_lists_select.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -561,3 +572,63 @@ def encn256v32_lists(values, list_ptr, d1=False, start0=None, nunits=None, out=N
     if trim:
         out = out[:int(offsets[nunits].item())]
     return out, offsets
+
+
+# ---- the read side of a resident index (include/turbopfor_gpu.h tpf_p4ndec256v32_lists_select) ----
+def lists_unit_base(list_ptr, out=None, err=None, ws=None):
+    """The unit directory of a lists stream, on the device: out[j] = the first
+    unit of list j, out[nlists] = the stream's unit count (the device form of
+    lists_units(list_ptr)[1]).  list_ptr: int64 CUDA tensor [nlists + 1]; out:
+    int32 CUDA tensor [nlists + 1]; err: optional int64 CUDA tensor [1] (-1 =
+    clean; j: list_ptr decreases at j; nlists: more than 0x7FFFFFFF units).
+    Asynchronous: no device-to-host read."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    if out is None:
+        out = torch.empty(nlists + 1, dtype=torch.int32, device=list_ptr.device)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_unit_base_workspace_size(nlists))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=list_ptr.device)
+    _check(L.tpf_lists_unit_base(_ptr(list_ptr), nlists, _ptr(out), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out
+
+
+def decn256v32_lists_select(packed, offsets, list_ptr, list_unit, sel, d1=False, start0=None, out=None, out_ptr=None, err=None,
+                            ws=None):
+    """Decode lists sel[0 .. nsel) of a resident lists stream, in the order
+    given, into one dense output: selection k lands at
+    out[out_ptr[k]:out_ptr[k+1]].  packed / offsets / list_ptr: the stream as
+    decn256v32_lists reads it; list_unit: int32 CUDA tensor [nlists + 1] from
+    lists_unit_base; sel: int32 CUDA tensor of list ids, any order, repeats
+    allowed; start0: optional int32 CUDA tensor [nlists], indexed by the lists
+    of the index (d1 only; None = 0).  out: int32 CUDA tensor whose numel() is
+    the capacity in values -- pass one sized for the selection, not for the
+    index: the work is sized by it (default: sized from list_ptr and sel, which
+    costs a device-to-host read; pass out to stay asynchronous).  out_ptr:
+    int64 CUDA tensor [nsel + 1], written; err: optional int64 CUDA tensor [1]
+    (-1 = clean).  Returns (out, out_ptr)."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nsel = sel.numel()
+    if out is None:
+        total = 0
+        if nsel and nlists > 0:
+            idx = sel.long() & 0xFFFFFFFF
+            ok = idx < nlists
+            idx = idx.clamp(max=nlists - 1)
+            total = int(((list_ptr[idx + 1] - list_ptr[idx]).clamp(min=0) * ok).sum().item())
+        out = torch.empty(max(total, 1), dtype=torch.int32, device=packed.device)[:total]
+    if out_ptr is None:
+        out_ptr = torch.empty(nsel + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_p4ndec256v32_lists_select_workspace_size(nsel, out.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_p4ndec256v32_lists_select(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
+                                           int(bool(d1)), _ptr(start0), _ptr(sel), nsel, _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws),
+                                           ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
