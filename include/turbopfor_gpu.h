@@ -364,6 +364,132 @@ int tpf_p4ndec256v32_lists_select(const uint8_t *d_in, uint64_t in_bytes, const 
                                   uint64_t out_values, uint64_t *d_out_ptr /* nsel + 1 */, void *d_ws, size_t ws_bytes,
                                   uint64_t *d_err, void *stream);
 
+/* ---- block-range reads of a resident index --------------------------------------
+ * A conjunctive query pairs a short list with a long one and needs only the
+ * few 256-value blocks of the long list whose doc-id range the short list
+ * reaches.  The three entry points below add the SKIP TABLE every CPU user of
+ * this codec keeps -- one uint32 per unit, the last value of that unit -- a
+ * search from doc-id ranges to unit ranges over it, and a decode of unit ranges
+ * of selected lists.  They compose on the device with no host step.
+ *
+ * tpf_lists_unit_last builds the skip table of a DELTA-1 lists stream, once per
+ * index, to be kept beside d_off, d_list_ptr and d_list_unit.
+ *   - Input: exactly what tpf_p4ndec256v32_lists takes with d1 != 0 (stream,
+ *     offsets, CSR pointers, d_start0 or NULL for 0), minus the output array.
+ *   - d_unit_last[u] (nunits entries, written) is the last decoded value of
+ *     unit u, mod 2^32: for unit i of list j the value at position
+ *     min(256 (i+1), n_j) - 1 of the list.  Tail units are included.
+ *   - Errors through d_err (optional; UINT64_MAX = clean), as
+ *     tpf_p4ndec256v32_lists reports them: < nunits the first unit whose parse
+ *     disagrees with its offsets; nunits + j the first list j with ptr[j+1] <
+ *     ptr[j]; nunits + nlists the lists' unit counts do not add up to nunits.
+ *     There is no output array, so the pointers are not held against
+ *     out_values.  On either list-structure error nothing is written to
+ *     d_unit_last.
+ *   - Cost: the index is read once and never decoded into a value-sized
+ *     buffer; the workspace is O(nunits + nlists).  A fixed number of launches.
+ *   - TPF_EINVAL (decided before any device call): nunits or nlists above
+ *     0x7FFFFFFF; with both non-zero a null d_in, d_off, d_list_ptr,
+ *     d_unit_last or d_ws, or ws_bytes below
+ *     tpf_lists_unit_last_workspace_size(nunits, nlists).  nunits == 0 or
+ *     nlists == 0 is a successful no-op that sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy. */
+size_t tpf_lists_unit_last_workspace_size(uint64_t nunits, uint64_t nlists);
+int tpf_lists_unit_last(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                        const uint64_t *d_list_ptr, uint64_t nlists, const uint32_t *d_start0,
+                        uint32_t *d_unit_last /* nunits */, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
+/* tpf_lists_range_units answers nq range queries over the skip table: query k
+ * asks for the units of list j = d_qlist[k] that can hold a value in
+ * [d_qlo[k], d_qhi[k]], both ends inclusive.
+ *   - With ua = d_list_unit[j] and ub = d_list_unit[j+1]: a is the first unit
+ *     of [ua, ub) with d_unit_last >= lo, b the first with d_unit_last >= hi, or
+ *     ub - 1 if there is none.  d_ufirst[k] = a - ua (list-relative) and
+ *     d_ucount[k] = b - a + 1.  With no such a, with lo > hi, or for an empty
+ *     list the result is (0, 0).  The named units are a superset of the units
+ *     holding a value in range by at most one unit at the top end (the list's
+ *     last unit when hi lies past the list).
+ *   - Precondition: the list ascends without wrapping mod 2^32.  For a list
+ *     that wraps, which units are named is unspecified, but the result still
+ *     lies inside the list: d_ufirst + d_ucount <= ub - ua.
+ *   - The outputs feed tpf_p4ndec256v32_lists_units unchanged, on the same
+ *     stream: d_qlist as d_sel, d_ufirst and d_ucount as they are.
+ *   - Errors through d_err (optional; UINT64_MAX = clean): the first query k
+ *     with d_qlist[k] >= nlists, ub < ua or ub > nunits.  Such a query gets
+ *     (0, 0) -- it decodes nothing -- and every other query is still answered.
+ *     The values are checked, never followed.
+ *   - One thread per query, two binary searches (12 dependent loads each for a
+ *     list of 4,096 units); one launch, sized by nq alone.
+ *   - TPF_EINVAL (decided before any device call): nlists, nunits or nq above
+ *     0x7FFFFFFF; with nq non-zero a null d_list_unit, d_unit_last, d_qlist,
+ *     d_qlo, d_qhi, d_ufirst or d_ucount.  nq == 0 is a successful no-op that
+ *     sets d_err to clean.
+ *   - Everything is enqueued on `stream`. */
+int tpf_lists_range_units(const uint32_t *d_list_unit, const uint32_t *d_unit_last, uint64_t nlists, uint64_t nunits,
+                          const uint32_t *d_qlist, const uint32_t *d_qlo, const uint32_t *d_qhi, uint64_t nq,
+                          uint32_t *d_ufirst, uint32_t *d_ucount, uint64_t *d_err, void *stream);
+
+/* tpf_p4ndec256v32_lists_units decodes unit ranges of selected lists of a
+ * resident stream into one dense output: selection k names units
+ * [d_ufirst[k], d_ufirst[k] + d_ucount[k]) of list j = d_sel[k], list-relative.
+ *   - Lists may come in any order; the same list may repeat, with the same or
+ *     different ranges, each occurrence getting its own copy; d_ucount[k] == 0
+ *     is allowed anywhere, any number in a row.
+ *   - Output layout: selection k yields 256 * ucount values, or
+ *     256 * (ucount - 1) + n_j % 256 when the range reaches the list's p4Enc32
+ *     tail unit, written to d_out + d_out_ptr[k]; d_out_ptr (nsel + 1 entries,
+ *     written) is a CSR array starting at 0, so the output is dense and in
+ *     selection order.  The value at list position p of a selected unit is bit
+ *     for bit what tpf_p4ndec256v32_lists writes at ptr[j] + p.
+ *   - Delta-1: with d1 != 0 d_unit_last (tpf_lists_unit_last) is required.
+ *     Source unit su of list j starts from d_start0[j] (NULL means 0) when it is
+ *     the list's first unit, else from d_unit_last[su - 1].  Every selected
+ *     block is read and decoded ONCE: there is no sums pass, and the launch
+ *     count is that of the plain form.  The table holds values, not indices: a
+ *     wrong table gives wrong values and never an out-of-range access.  With
+ *     d1 == 0 d_unit_last and d_start0 are ignored, so a frequency list stored
+ *     in parallel is read over the unit ranges found for its doc-id list.
+ *   - Output bounds: nothing is written at or past d_out + out_values, and
+ *     nothing outside [d_out_ptr[k], d_out_ptr[k+1]) for any k.  d_out is only
+ *     4-byte aligned.
+ *   - Cost: as tpf_p4ndec256v32_lists_select.  No kernel is sized by nlists or
+ *     nunits, and no pass reads the index at a unit that is not selected --
+ *     but for d_list_ptr[j+1] and d_list_unit[j+1] of a selected list, the end
+ *     offset of a selected unit, and with d1 d_unit_last of the unit before a
+ *     selected one.  Grids and the workspace are sized on the host from nsel
+ *     and out_values alone (a selection that fits holds at most
+ *     out_values/256 + nsel units).  Ten launches (two of them reset d_err and
+ *     the workspace header), whatever the selection, d1 or plain.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       < nunits        the lowest SOURCE unit index among the selected units
+ *                       whose parse disagrees with its offsets;
+ *       nunits + k      the first selection k refused by any check of
+ *                       tpf_p4ndec256v32_lists_select, or with d_ufirst[k] +
+ *                       d_ucount[k] (summed without 32-bit wrap) above the unit
+ *                       count of list j: nothing is written to d_out or
+ *                       d_out_ptr;
+ *       nunits + nsel   the selected values do not fit out_values: nothing is
+ *                       written to d_out, but d_out_ptr is filled completely.
+ *   - TPF_EINVAL (decided before any device call): with nsel non-zero a null
+ *     d_sel, d_ufirst, d_ucount, d_out_ptr, d_in, d_off, d_list_ptr,
+ *     d_list_unit, d_out or d_ws, a null d_unit_last when d1 != 0, or ws_bytes
+ *     below tpf_p4ndec256v32_lists_units_workspace_size(nsel, out_values);
+ *     nlists, nunits, nsel or out_values/256 + nsel above 0x7FFFFFFF.
+ *     nsel == 0 is a successful no-op that writes d_out_ptr[0] = 0 and sets
+ *     d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_p4ndec256v32_lists_units_workspace_size(uint64_t nsel, uint64_t out_values);
+int tpf_p4ndec256v32_lists_units(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                                 const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists, int d1,
+                                 const uint32_t *d_start0, const uint32_t *d_unit_last, const uint32_t *d_sel,
+                                 const uint32_t *d_ufirst, const uint32_t *d_ucount, uint64_t nsel, uint32_t *d_out,
+                                 uint64_t out_values, uint64_t *d_out_ptr /* nsel + 1 */, void *d_ws, size_t ws_bytes,
+                                 uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

@@ -581,6 +581,80 @@ int tpf_p4ndec256v32_lists_select(const uint8_t * d_in, uint64_t in_bytes, const
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_select");
 }
 
+// ---- block-range reads of a resident index: the skip table, the range search
+// and the decode of unit ranges.  Arguments are judged before the device is
+// looked for.
+size_t tpf_lists_unit_last_workspace_size(uint64_t nunits, uint64_t nlists) { return tpf::lists_unit_last_workspace(nunits, nlists); }
+
+int tpf_lists_unit_last(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                        uint64_t nlists, const uint32_t * d_start0, uint32_t * d_unit_last, void * d_ws, size_t ws_bytes, uint64_t * d_err,
+                        void * stream)
+{
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_unit_last: nunits and nlists are limited to 0x7FFFFFFF");
+    if (nunits && nlists && (!d_in || !d_off || !d_list_ptr || !d_unit_last || !d_ws))
+        return fail(TPF_EINVAL, "tpf_lists_unit_last: null pointer");
+    if (nunits && nlists && ws_bytes < tpf_lists_unit_last_workspace_size(nunits, nlists))
+        return fail(TPF_EINVAL, "tpf_lists_unit_last: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_unit_last(d_in, in_bytes, d_off, nunits, d_list_ptr, nlists, d_start0, d_unit_last, d_ws,
+                                               reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_unit_last");
+}
+
+int tpf_lists_range_units(const uint32_t * d_list_unit, const uint32_t * d_unit_last, uint64_t nlists, uint64_t nunits,
+                          const uint32_t * d_qlist, const uint32_t * d_qlo, const uint32_t * d_qhi, uint64_t nq, uint32_t * d_ufirst,
+                          uint32_t * d_ucount, uint64_t * d_err, void * stream)
+{
+    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_range_units: nlists, nunits and nq are limited to 0x7FFFFFFF");
+    if (nq && (!d_list_unit || !d_unit_last || !d_qlist || !d_qlo || !d_qhi || !d_ufirst || !d_ucount))
+        return fail(TPF_EINVAL, "tpf_lists_range_units: null pointer");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_range_units(d_list_unit, d_unit_last, nlists, nunits, d_qlist, d_qlo, d_qhi, nq, d_ufirst, d_ucount,
+                                                 reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_range_units");
+}
+
+size_t tpf_p4ndec256v32_lists_units_workspace_size(uint64_t nsel, uint64_t out_values)
+{
+    return tpf::lists_units_workspace(nsel, out_values);
+}
+
+int tpf_p4ndec256v32_lists_units(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits,
+                                 const uint64_t * d_list_ptr, const uint32_t * d_list_unit, uint64_t nlists, int d1,
+                                 const uint32_t * d_start0, const uint32_t * d_unit_last, const uint32_t * d_sel,
+                                 const uint32_t * d_ufirst, const uint32_t * d_ucount, uint64_t nsel, uint32_t * d_out, uint64_t out_values,
+                                 uint64_t * d_out_ptr, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nsel > 0x7FFFFFFFull
+        || (nsel && tpf::lists_select_unit_cap(nsel, out_values) > 0x7FFFFFFFull))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: nlists, nunits, nsel and out_values / 256 + nsel are limited to 0x7FFFFFFF");
+    if (nsel && (!d_sel || !d_ufirst || !d_ucount || !d_out_ptr || !d_in || !d_off || !d_list_ptr || !d_list_unit || !d_out || !d_ws))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: null pointer");
+    if (nsel && d1 && !d_unit_last)
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: null d_unit_last (delta-1 needs the skip table of tpf_lists_unit_last)");
+    if (nsel && ws_bytes < tpf_p4ndec256v32_lists_units_workspace_size(nsel, out_values))
+        return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_units(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
+                                           d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_sel, d_ufirst, d_ucount, nsel, d_out,
+                                           out_values, d_out_ptr, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_units");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

@@ -77,6 +77,25 @@ hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint
                                const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
                                uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
                                hipStream_t s);
+// block-range reads of a resident index (p4_lists_units.hip):
+// the skip table of a delta-1 stream (the last value of every unit), the
+// search from doc-id ranges to unit ranges, and the decode of unit ranges of
+// selected lists.  Passes of the build: structure -> phase A and its run scan
+// -> one prefix per list -> the tails' sums -> the write pass.  Passes of the
+// decode: plan over the SELECTION -> two run scans -> heads -> full blocks ->
+// tails, the same for delta-1 (a unit starts from the table) and plain.
+size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists);
+hipError_t launch_lists_unit_last(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                                  uint64_t nlists, const uint32_t * start0, uint32_t * unit_last, void * ws, unsigned long long * err,
+                                  hipStream_t s);
+hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t * unit_last, uint64_t nlists, uint64_t nunits,
+                                    const uint32_t * qlist, const uint32_t * qlo, const uint32_t * qhi, uint64_t nq, uint32_t * ufirst,
+                                    uint32_t * ucount, unsigned long long * err, hipStream_t s);
+size_t lists_units_workspace(uint64_t nsel, uint64_t out_values);
+hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                              const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
+                              const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount, uint64_t nsel, uint32_t * out,
+                              uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

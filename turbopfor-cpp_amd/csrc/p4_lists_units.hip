@@ -1,0 +1,741 @@
+// p4_lists_units.hip -- block-range reads of a resident index (p4_lists.h,
+// DESIGN.md 4.10): tpf_lists_unit_last builds the SKIP TABLE of a delta-1 lists
+// stream once (the last value of every unit), tpf_lists_range_units turns
+// doc-id ranges into unit ranges with it, and tpf_p4ndec256v32_lists_units
+// decodes unit ranges of selected lists into one dense output.  The decode
+// follows the selective decode's virtual-unit scheme (p4_lists_select.hip):
+// the selected unit ranges, laid end to end in selection order, are the
+// virtual unit sequence; virtual unit v of selection k is source unit
+// list_unit[sel[k]] + ufirst[k] + (v - vbase[k]).  With the table every unit
+// is decodable alone -- its start is the last value of the unit before it --
+// so delta-1 reads and decodes every selected block once, in the plain
+// form's launches.
+#include "p4_lists.h"
+
+#include "p4_dec256v32.h"
+#include "p4_lists_dev.h"
+#include "p4_generic.h"
+#include "p4_scan.h"
+#include "tpf_kernels.h"
+
+namespace tpf::dev
+{
+
+// ---- the skip table ---------------------------------------------------------
+struct UlArgs
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    uint64_t nunits;
+    const uint64_t * ptr;
+    uint64_t nlists;
+    const uint32_t * start0;
+    const ListsHdr * hdr;
+    const uint32_t * rec;      // unit records (p4_lists.h)
+    const uint32_t * ubase;    // first unit of every list
+    const uint32_t * sums;     // block sums of phase A (tails 0)
+    const uint32_t * run_pre;  // run scan of phase A's 64-unit runs
+    const uint32_t * run_tile;
+    uint32_t * pbase;          // prefix of the block sums at ubase[j], j < nlists
+    uint32_t * tsum;           // sum of (v + 1) over list j's tail unit (lists with a tail only)
+    uint32_t * unit_last;
+    unsigned long long * err;
+};
+
+// pbase[j] = P(ubase[j]), P(x) = the sum of every block sum before unit x (mod
+// 2^32): the base of phase A's 64-unit run plus at most 63 sums.  (A list that
+// starts at nunits holds no unit: its entry is never read.)
+__global__ __launch_bounds__(256) void k_ul_pbase(const UlArgs A)
+{
+    if (!lists_go(A.hdr, A.nunits))
+        return;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; j < A.nlists; j += gsz)
+    {
+        const uint32_t x = A.ubase[j];
+        uint32_t acc = 0u;
+        if (x < A.nunits)
+        {
+            acc = run_base(A.run_pre, A.run_tile, x / kSumRun);
+            for (uint32_t q = x / kSumRun * kSumRun; q < x; ++q)
+                acc += A.sums[q];
+        }
+        A.pbase[j] = acc;
+    }
+}
+
+// The tails' sums: every wave owns kRunDefault consecutive LISTS with the
+// generic decoder's pipeline, as k_lists_tails does; lane t holds list first +
+// t's tail unit or nothing.  The decoded gaps are summed, not stored.
+template <uint32_t NC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ul_tails(const UlArgs A)
+{
+    __shared__ uint32_t slots[4][kListSlot / 4];
+    __shared__ uint32_t scratch[4][kListScratchU32];
+    if (!lists_go(A.hdr, A.nunits))
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= A.nlists)
+        return;
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nlists - first));
+    const uint64_t j = first + t;
+    const uint64_t p0 = t < n ? A.ptr[j] : 0ull;
+    const uint64_t p1 = t < n ? A.ptr[j + 1u] : 0ull;
+    const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
+    const bool has = cnt != 0u;
+    const uint64_t hasmask = __ballot(has);
+    if (hasmask == 0ull)
+        return;
+    const uint32_t u = has ? A.ubase[j] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
+    const uint64_t o = has ? A.off[u] : 0ull;
+    const uint64_t e = has ? A.off[u + 1u] : 0ull;
+    RunPlaneT<kListSlot> P;
+    P.init(in_base, in_end, o, e, has);
+    uint32_t sumv = 0u;
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((hasmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        const uint32_t cj = rl(cnt, jj);
+        uint32_t v[4], cm;
+        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, v, &cm);
+        uint32_t loc = 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+            loc += t + 64u * q < cj ? v[q] + 1u : 0u;
+        const uint32_t sm = wave_sum(loc);
+        sumv = t == jj ? sm : sumv;
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+    bool more = true;
+    for (uint32_t jb = 0; more; jb += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
+                consume(C[q], jb + q);
+                more = jb + q + 1 < n;
+            }
+        }
+    }
+    if (has)
+        A.tsum[j] = sumv;
+    // units ascend with the lists: the first bad lane is the lowest unit
+    if (A.err != nullptr && badmask != 0u && t == static_cast<uint32_t>(__builtin_ctzll(badmask)))
+        atomicMin(A.err, static_cast<unsigned long long>(u));
+}
+
+// The write pass: every wave owns one of phase A's 64-unit runs, lane t unit
+// first + t.  last(u) = start0[list] + P(u + 1) - P(ubase[list]) mod 2^32, a
+// tail adding its own sum (phase A counts it 0); the list of every unit from
+// the head records inside the run and one search for the run's first unit.
+__global__ __launch_bounds__(256) void k_ul_write(const UlArgs A)
+{
+    if (!lists_go(A.hdr, A.nunits))
+        return;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kSumRun;
+    if (first >= A.nunits)
+        return;
+    const uint32_t n = static_cast<uint32_t>(min_u64(kSumRun, A.nunits - first));
+    const bool valid = t < n;
+    const uint64_t u = first + t;
+    const uint32_t r = valid ? A.rec[u] : 0u;
+    const uint32_t r0 = rl(r, 0) & kRecList;
+    const uint32_t j0 = r0 != 0u ? r0 - 1u : find_list(A.ubase, static_cast<uint32_t>(A.nlists), static_cast<uint32_t>(first), t);
+    const uint32_t id = umax32(wave_incl_max(r & kRecList), j0 + 1u) - 1u;
+    const uint32_t sv = valid ? A.sums[u] : 0u;
+    const uint32_t p1 = run_base(A.run_pre, A.run_tile, first / kSumRun) + wave_incl_scan(sv);
+    if (valid)
+    {
+        const uint32_t s0 = A.start0 != nullptr ? A.start0[id] : 0u;
+        const uint32_t ts = (r & kRecTail) != 0u ? A.tsum[id] : 0u;
+        A.unit_last[u] = s0 + p1 - A.pbase[id] + ts;
+    }
+}
+
+// ---- doc-id ranges to unit ranges -----------------------------------------------
+// One thread per query: two binary searches over the list's slice of the skip
+// table.  Every index is checked against nlists / nunits before it is used.
+__global__ __launch_bounds__(256) void k_range_units(const uint32_t * __restrict list_unit, const uint32_t * __restrict unit_last,
+                                                      uint64_t nlists, uint64_t nunits, const uint32_t * __restrict qlist,
+                                                      const uint32_t * __restrict qlo, const uint32_t * __restrict qhi, uint64_t nq,
+                                                      uint32_t * __restrict ufirst, uint32_t * __restrict ucount,
+                                                      unsigned long long * __restrict err)
+{
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; k < nq; k += gsz)
+    {
+        const uint32_t j = qlist[k];
+        const uint32_t lo = qlo[k], hi = qhi[k];
+        uint32_t uf = 0u, uc = 0u;
+        bool bad = j >= nlists;
+        if (!bad)
+        {
+            const uint32_t ua = list_unit[j], ub = list_unit[j + 1u];
+            bad = ub < ua || ub > nunits;
+            if (!bad && lo <= hi && ua < ub)
+            {
+                // a: the first unit of [ua, ub) whose last value is >= lo
+                uint32_t a = ua, x = ub;
+                while (a < x)
+                {
+                    const uint32_t m = a + (x - a) / 2u;
+                    if (unit_last[m] >= lo)
+                        x = m;
+                    else
+                        a = m + 1u;
+                }
+                if (a < ub)
+                {
+                    // b: the first unit of [a, ub) whose last value is >= hi, or the list's last unit
+                    uint32_t b = a;
+                    x = ub;
+                    while (b < x)
+                    {
+                        const uint32_t m = b + (x - b) / 2u;
+                        if (unit_last[m] >= hi)
+                            x = m;
+                        else
+                            b = m + 1u;
+                    }
+                    if (b == ub)
+                        b = ub - 1u;
+                    uf = a - ua;
+                    uc = b - a + 1u;
+                }
+            }
+        }
+        ufirst[k] = uf;
+        ucount[k] = uc;
+        if (bad && err != nullptr)
+            atomicMin(err, static_cast<unsigned long long>(k));
+    }
+}
+
+// ---- the decode of unit ranges -------------------------------------------------
+struct UnHdr
+{
+    unsigned long long bad;    // first refused selection k (~0: none)
+    unsigned long long vtotal; // virtual units: the sum of the selections' unit counts
+    unsigned long long ototal; // selected values: d_out_ptr[nsel]
+};
+
+// go / no-go: every selection is sound and the selected values fit the output
+// (then vtotal <= vcap follows, a range of n values holding at most n/256 + 1
+// units; it is checked all the same: vcap sizes the records)
+__device__ __forceinline__ bool un_go(const UnHdr * h, uint64_t out_values, uint64_t vcap)
+{
+    return h->bad == ~0ull && h->ototal <= out_values && h->vtotal <= vcap;
+}
+
+struct UnArgs
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    const uint32_t * list_unit;
+    const uint32_t * start0;
+    const uint32_t * unit_last; // delta-1: the skip table (values, never indices)
+    const uint32_t * sel;
+    const uint32_t * ufirst;
+    const uint32_t * ucount;
+    uint64_t nsel;
+    uint32_t * out;
+    uint64_t out_values;
+    uint64_t vcap;             // the host's cap on the virtual units: out_values / 256 + nsel
+    const uint64_t * out_ptr;  // d_out_ptr (written by the heads pass)
+    const UnHdr * hdr;
+    const uint32_t * rec;      // records of the virtual units (p4_lists.h)
+    const uint32_t * vbase;    // first virtual unit of every selection, nsel + 1
+    unsigned long long * err;
+};
+
+// Plan: one thread per SELECTION -- the unit and value counts of its range for
+// the two run scans, and the checks of everything the later passes index with
+// (the values are checked here, never followed) -- and the records of the
+// virtual units zeroed for the heads pass, up to the host's cap.  A range
+// holds 256 values per unit, but n % 256 in the list's p4Enc32 tail unit.
+__global__ __launch_bounds__(256) void k_un_plan(const uint64_t * __restrict ptr, const uint32_t * __restrict list_unit, uint64_t nlists,
+                                                  uint64_t nunits, const uint32_t * __restrict sel, const uint32_t * __restrict ufirst,
+                                                  const uint32_t * __restrict ucount, uint64_t nsel, uint32_t * __restrict totu,
+                                                  uint64_t * __restrict totv, UnHdr * __restrict hdr, uint32_t * __restrict rec,
+                                                  uint64_t vcap)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t k = gid; k < nsel; k += gsz)
+    {
+        const uint32_t j = sel[k];
+        const uint64_t uf = ufirst[k], uc = ucount[k];
+        bool bad = j >= nlists;
+        uint64_t nv = 0u;
+        if (!bad)
+        {
+            const uint64_t a = ptr[j], b = ptr[j + 1u];
+            const uint32_t ua = list_unit[j], ub = list_unit[j + 1u];
+            bad = b < a || ub < ua || ub > nunits;
+            if (!bad)
+            {
+                const uint64_t n = b - a;
+                const uint32_t units = list_units(n);
+                bad = ub - ua != units || uf + uc > units; // 64-bit: the sum cannot wrap
+                if (!bad)
+                {
+                    const uint32_t r = static_cast<uint32_t>(n & 255u);
+                    nv = 256u * uc - ((uc != 0u && uf + uc == units && r != 0u) ? 256u - r : 0u);
+                }
+            }
+        }
+        totu[k] = bad ? 0u : static_cast<uint32_t>(uc);
+        totv[k] = bad ? 0ull : nv;
+        if (bad)
+            atomicMin(&hdr->bad, static_cast<unsigned long long>(k));
+    }
+    for (uint64_t u = gid; u < vcap; u += gsz)
+        rec[u] = 0u;
+}
+
+// Heads: the verdict (d_err for a refused selection or an output that is too
+// small), d_out_ptr, then per selection its virtual unit base and the records
+// of its first unit and of its tail -- the head carries k + 1, the SELECTION.
+// A range has a tail to decode exactly when its value count is no multiple of
+// 256: it reaches the list's last unit and that unit is a p4Enc32 tail.
+__global__ __launch_bounds__(256) void k_un_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap,
+                                                   const uint32_t * __restrict totu, const uint64_t * __restrict totv,
+                                                   const uint64_t * __restrict preu, const uint64_t * __restrict tileu,
+                                                   const uint64_t * __restrict prev, const uint64_t * __restrict tilev,
+                                                   const UnHdr * __restrict hdr, uint32_t * __restrict vbase, uint32_t * __restrict rec,
+                                                   uint64_t * __restrict out_ptr, unsigned long long * __restrict err)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    if (hdr->bad != ~0ull)
+    {
+        if (gid == 0 && err != nullptr)
+            *err = nunits + hdr->bad;
+        return;
+    }
+    const bool go = un_go(hdr, out_values, vcap);
+    for (uint64_t k = gid; k < nsel; k += gsz)
+        out_ptr[k] = run_base(prev, tilev, k);
+    if (gid == 0)
+    {
+        out_ptr[nsel] = hdr->ototal;
+        if (!go && err != nullptr)
+            *err = nunits + nsel;
+    }
+    if (!go)
+        return;
+    for (uint64_t k = gid; k < nsel; k += gsz)
+    {
+        const uint32_t vb = static_cast<uint32_t>(run_base(preu, tileu, k)); // <= vtotal <= vcap < 2^31
+        vbase[k] = vb;
+        const uint32_t units = totu[k];
+        const bool tail = (totv[k] & 255u) != 0u;
+        if (units == 1u)
+            rec[vb] = static_cast<uint32_t>(k + 1u) | (tail ? kRecTail : 0u);
+        else if (units != 0u)
+        {
+            rec[vb] = static_cast<uint32_t>(k + 1u);
+            if (tail)
+                rec[vb + units - 1u] = kRecTail;
+        }
+    }
+    if (gid == 0)
+        vbase[nsel] = static_cast<uint32_t>(hdr->vtotal);
+}
+
+// Full blocks: every wave owns a run of kRunDefault consecutive VIRTUAL units
+// with the k_dec256v32w pipeline, as k_sel_dec does.  Lane t resolves the
+// selection k of virtual unit first + t from the head records inside the run
+// and one search over vbase for the run's first unit, gathers sel[k],
+// ufirst[k] and list_unit[sel[k]] and loads the offsets of its SOURCE unit.
+// Delta-1: the start of source unit su is one more gather -- start0[list] for
+// the list's first unit, else unit_last[su - 1] (su - 1 is a unit of the same
+// list: in range whatever the table holds) -- settled with the output plane's
+// gathers before the chunks go in flight.  The output of a run is one
+// contiguous range: one buffer descriptor, stores past it dropped.
+template <bool D1, uint32_t NC, int MINW>
+__global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
+{
+    __shared__ uint32_t slots[4][kSlotBytes / 4];
+    __shared__ uint32_t scratch[4][kWaveScratchU32];
+    // the run's source units, for the error report only (k_sel_dec: held in a
+    // register across the pipeline they cost spilled VGPRs at 7 waves)
+    __shared__ uint32_t srcu[4][kRunDefault];
+    if (!un_go(A.hdr, A.out_values, A.vcap))
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    uint32_t * scr = scratch[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t vt = A.hdr->vtotal;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= vt)
+        return; // the grid is sized by the host's cap
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, vt - first));
+    const bool valid = t < n;
+    const uint64_t v = first + t;
+    const uint32_t r = valid ? A.rec[v] : 0u;
+    const bool full = valid && (r & kRecTail) == 0u;
+    const uint64_t fullmask = __ballot(full);
+    if (fullmask == 0ull)
+        return; // a run of tails only
+
+    // ---- the selection of every unit: heads inside the run, the search before it
+    const uint32_t r0 = rl(r, 0) & kRecList;
+    const uint32_t k0 = r0 != 0u ? r0 - 1u : find_list(A.vbase, static_cast<uint32_t>(A.nsel), static_cast<uint32_t>(first), t);
+    const uint32_t id = umax32(wave_incl_max(r & kRecList), k0 + 1u) - 1u;
+    const uint32_t vb = valid ? A.vbase[id] : 0u;
+    const uint32_t lj = valid ? A.sel[id] : 0u;
+    const uint32_t inl = static_cast<uint32_t>(v) - vb;          // unit v - vb of its range
+    const uint32_t inu = (valid ? A.ufirst[id] : 0u) + inl;      // ... and unit inu of its list
+    // the source unit: the plan checked sel[k] < nlists, ufirst + ucount <= units_j and list_unit[j] + units_j <= nunits
+    const uint32_t su = full ? A.list_unit[lj] + inu : 0u;
+    const uint64_t o = full ? A.off[su] : 0ull;
+    const uint64_t e = full ? A.off[su + 1u] : 0ull;
+    RunPlaneT<kSlotBytes, true> P;
+    P.init(in_base, in_end, o, e, full);
+    if (t < kRun)
+        srcu[wv][t] = full ? su : 0xFFFFFFFFu;
+
+    const uint64_t opos = (valid ? A.out_ptr[id] : 0ull) + 256ull * inl;
+    const uint64_t opos0 = readlane_u64(opos, 0);
+    const uint32_t rel = static_cast<uint32_t>(opos - opos0) * 4u; // bytes from the run's first value
+    const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
+    const __amdgpu_buffer_rsrc_t ors = make_rsrc(A.out + opos0, rl(rel, lastf) + 1024u);
+    uint32_t startv = 0u;
+    if constexpr (D1)
+    {
+        if (full)
+            startv = inu == 0u ? (A.start0 != nullptr ? A.start0[lj] : 0u) : A.unit_last[su - 1u];
+    }
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((fullmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        u32x4 x;
+        const uint32_t used = decode_block256v32(slot, (ctl >> kCtlShift) & 15u, P.head(c, ctl, slot), scr, t, x);
+        if constexpr (D1)
+            apply_delta1_256(x, rl(startv, jj));
+        st16_run(ors, rl(rel, jj) + 16u * t, x);
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+
+    bool more = true;
+    for (uint32_t j = 0; more; j += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], j + q + NC - 1, t);
+                consume(C[q], j + q);
+                more = j + q + 1 < n;
+            }
+        }
+    }
+    if (A.err != nullptr && badmask != 0u)
+    {
+        // in stream numbering; the source units of a run do not ascend
+        const uint32_t m = wave_min((t < kRun && ((badmask >> t) & 1ull) != 0ull) ? srcu[wv][t] : 0xFFFFFFFFu);
+        if (t == 0)
+            atomicMin(A.err, static_cast<unsigned long long>(m));
+    }
+}
+
+// Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
+// decoder's pipeline, as k_sel_tails does; lane t holds selection first + t's
+// tail unit -- the last unit of its range, n % 256 values at the end of the
+// selection's output -- or nothing.  Delta-1: the tail starts from the last
+// value of the unit before it, or from start0 in a tail-only list.
+template <bool D1, uint32_t NC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_un_tails(const UnArgs A)
+{
+    __shared__ uint32_t slots[4][kListSlot / 4];
+    __shared__ uint32_t scratch[4][kListScratchU32];
+    if (!un_go(A.hdr, A.out_values, A.vcap))
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= A.nsel)
+        return;
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nsel - first));
+    const uint64_t k = first + t;
+    const uint64_t p0 = t < n ? A.out_ptr[k] : 0ull;
+    const uint64_t p1 = t < n ? A.out_ptr[k + 1u] : 0ull;
+    const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
+    const bool has = cnt != 0u;
+    const uint64_t hasmask = __ballot(has);
+    if (hasmask == 0ull)
+        return;
+    const uint32_t lj = has ? A.sel[k] : 0u;
+    const uint32_t inu = has ? A.ufirst[k] + A.ucount[k] - 1u : 0u; // the list's last unit (ucount >= 1)
+    const uint32_t su = has ? A.list_unit[lj] + inu : 0u;
+    const uint64_t o = has ? A.off[su] : 0ull;
+    const uint64_t e = has ? A.off[su + 1u] : 0ull;
+    RunPlaneT<kListSlot> P;
+    P.init(in_base, in_end, o, e, has);
+    const uint64_t opos = p1 - cnt;
+    uint32_t startv = 0u;
+    if constexpr (D1)
+    {
+        if (has)
+            startv = inu == 0u ? (A.start0 != nullptr ? A.start0[lj] : 0u) : A.unit_last[su - 1u];
+    }
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((hasmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        const uint32_t cj = rl(cnt, jj);
+        uint32_t x[4], cm;
+        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
+        if constexpr (D1)
+            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        uint32_t * op = A.out + readlane_u64(opos, jj);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+            if (t + 64u * q < cj)
+                __builtin_nontemporal_store(x[q], op + t + 64u * q);
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+    bool more = true;
+    for (uint32_t jb = 0; more; jb += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
+                consume(C[q], jb + q);
+                more = jb + q + 1 < n;
+            }
+        }
+    }
+    if (A.err != nullptr && badmask != 0u)
+    {
+        const uint32_t m = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
+        if (t == 0)
+            atomicMin(A.err, static_cast<unsigned long long>(m));
+    }
+}
+
+} // namespace tpf::dev
+
+namespace tpf
+{
+
+namespace
+{
+size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
+
+// Workspace of the skip-table build: header | run scan of the lists' unit
+// counts | ubase (nlists + 1) | pbase (nlists) | tail sums (nlists) | unit
+// records (nunits) | phase A (the chained decode's layout over nunits units),
+// each 256-byte aligned.  Nothing in it is sized by the values.
+struct UlWs
+{
+    dev::ListsHdr * hdr;
+    RunScanWs<uint64_t> scan;
+    uint32_t *ubase, *pbase, *tsum, *rec;
+    uint8_t * chain;
+    size_t bytes;
+
+    UlWs(void * ws, uint64_t nunits, uint64_t nlists)
+    {
+        auto * p = static_cast<uint8_t *>(ws);
+        size_t x = 0;
+        hdr = reinterpret_cast<dev::ListsHdr *>(p + x);
+        x += 256u;
+        scan = RunScanWs<uint64_t>::carve(p + x, nlists);
+        x += al256(RunScanWs<uint64_t>::bytes(nlists));
+        ubase = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * (nlists + 1u));
+        pbase = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * nlists);
+        tsum = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * nlists);
+        rec = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * nunits);
+        chain = p + x;
+        x += al256(d1chain_workspace(nunits));
+        bytes = x;
+    }
+};
+
+// Workspace of the units decode: header | run scan of the selections' unit
+// counts | their value counts and that scan (u64) | vbase (nsel + 1) | records
+// of the virtual units (vcap), each 256-byte aligned.
+struct UnWs
+{
+    dev::UnHdr * hdr;
+    RunScanWs<uint64_t> scanu;
+    uint64_t *totv, *prev, *tilev;
+    uint32_t *vbase, *rec;
+    size_t bytes;
+
+    UnWs(void * ws, uint64_t nsel, uint64_t vcap)
+    {
+        auto * p = static_cast<uint8_t *>(ws);
+        size_t x = 0;
+        hdr = reinterpret_cast<dev::UnHdr *>(p + x);
+        x += 256u;
+        scanu = RunScanWs<uint64_t>::carve(p + x, nsel);
+        x += al256(RunScanWs<uint64_t>::bytes(nsel));
+        totv = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * nsel);
+        prev = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * nsel);
+        tilev = reinterpret_cast<uint64_t *>(p + x);
+        x += al256(8u * RunScanWs<uint64_t>::tiles(nsel)) + 256u;
+        vbase = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * (nsel + 1u));
+        rec = reinterpret_cast<uint32_t *>(p + x);
+        x += al256(4u * vcap);
+        bytes = x;
+    }
+};
+
+uint32_t flat_grid(uint64_t items, hipStream_t s)
+{
+    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
+}
+} // namespace
+
+size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists) { return UlWs(nullptr, nunits, nlists).bytes; }
+
+hipError_t launch_lists_unit_last(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                                  uint64_t nlists, const uint32_t * start0, uint32_t * unit_last, void * ws, unsigned long long * err,
+                                  hipStream_t s)
+{
+    if (nunits == 0 || nlists == 0)
+        return hipSuccess;
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    const UlWs W(ws, nunits, nlists);
+    // no value array to hold the pointers against: only their order is checked
+    hipError_t e = launch_lists_structure(ptr, nlists, ~0ull, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
+    if (e != hipSuccess)
+        return e;
+    ChainView cv;
+    if ((e = launch_lists_sums(in, in_bytes, off, nunits, W.rec, W.hdr, nlists, W.chain, &cv, err, s)) != hipSuccess)
+        return e;
+    const dev::UlArgs A{in, in_bytes, off, nunits, ptr, nlists, start0, W.hdr, W.rec, W.ubase, cv.sums, cv.pre, cv.tile,
+                        W.pbase, W.tsum, unit_last, err};
+    hipLaunchKernelGGL(dev::k_ul_pbase, dim3(flat_grid(nlists, s)), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    const uint32_t tgrid = static_cast<uint32_t>((nlists + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    hipLaunchKernelGGL((dev::k_ul_tails<dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    const uint32_t wgrid = static_cast<uint32_t>((nunits + 4u * dev::kSumRun - 1u) / (4u * dev::kSumRun));
+    hipLaunchKernelGGL(dev::k_ul_write, dim3(wgrid), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t * unit_last, uint64_t nlists, uint64_t nunits,
+                                    const uint32_t * qlist, const uint32_t * qlo, const uint32_t * qhi, uint64_t nq, uint32_t * ufirst,
+                                    uint32_t * ucount, unsigned long long * err, hipStream_t s)
+{
+    if (nq == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(dev::k_range_units, dim3(flat_grid(nq, s)), dim3(256), 0, s, list_unit, unit_last, nlists, nunits, qlist, qlo, qhi, nq,
+                       ufirst, ucount, err);
+    return hipGetLastError();
+}
+
+size_t lists_units_workspace(uint64_t nsel, uint64_t out_values)
+{
+    return UnWs(nullptr, nsel, lists_select_unit_cap(nsel, out_values)).bytes;
+}
+
+hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                              const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
+                              const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount, uint64_t nsel, uint32_t * out,
+                              uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s)
+{
+    if (nsel == 0)
+        return out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess;
+    const uint64_t vcap = lists_select_unit_cap(nsel, out_values);
+    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || (d1 && unit_last == nullptr))
+        return hipErrorInvalidValue;
+    const UnWs W(ws, nsel, vcap);
+    hipError_t e = fill_u32(W.hdr, 0xFFFFFFFFu, 2, s);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_un_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, ufirst,
+                       ucount, nsel, W.scanu.tot, W.totv, W.hdr, W.rec, vcap);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64(W.scanu.tot, nsel, W.scanu.pre, W.scanu.tile, reinterpret_cast<uint64_t *>(&W.hdr->vtotal), s)) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64t(W.totv, nsel, W.prev, W.tilev, reinterpret_cast<uint64_t *>(&W.hdr->ototal), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_un_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, W.scanu.tot, W.totv,
+                       W.scanu.pre, W.scanu.tile, W.prev, W.tilev, W.hdr, W.vbase, W.rec, out_ptr, err);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    const dev::UnArgs A{in, in_bytes, off, list_unit, start0, unit_last, sel, ufirst, ucount, nsel, out, out_values, vcap, out_ptr,
+                        W.hdr, W.rec, W.vbase, err};
+    // sized by the host's cap: waves past the real unit count exit
+    const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    const uint32_t tgrid = static_cast<uint32_t>((nsel + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    if (d1)
+        hipLaunchKernelGGL((dev::k_un_dec<true, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
+    else
+        hipLaunchKernelGGL((dev::k_un_dec<false, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if (d1)
+        hipLaunchKernelGGL((dev::k_un_tails<true, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
+    else
+        hipLaunchKernelGGL((dev::k_un_tails<false, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+} // namespace tpf

@@ -147,6 +147,19 @@ def lib():
             L.tpf_p4ndec256v32_lists_select.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64,
                                                         c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_p4ndec256v32_lists_select.restype = ctypes.c_int
+        # the skip table, the range search and the units decode: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_p4ndec256v32_lists_units"):
+            L.tpf_lists_unit_last_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_lists_unit_last_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_unit_last.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_unit_last.restype = ctypes.c_int
+            L.tpf_lists_range_units.argtypes = [c_vp, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp]
+            L.tpf_lists_range_units.restype = ctypes.c_int
+            L.tpf_p4ndec256v32_lists_units_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_p4ndec256v32_lists_units_workspace_size.restype = ctypes.c_size_t
+            L.tpf_p4ndec256v32_lists_units.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+                                                       c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_p4ndec256v32_lists_units.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -631,4 +644,99 @@ def decn256v32_lists_select(packed, offsets, list_ptr, list_unit, sel, d1=False,
     _check(L.tpf_p4ndec256v32_lists_select(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
                                            int(bool(d1)), _ptr(start0), _ptr(sel), nsel, _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws),
                                            ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
+
+
+# ---- block-range reads of a resident index (include/turbopfor_gpu.h tpf_lists_unit_last,
+# tpf_lists_range_units, tpf_p4ndec256v32_lists_units) ----
+def lists_unit_last(packed, offsets, list_ptr, start0=None, out=None, err=None, ws=None):
+    """The skip table of a delta-1 lists stream, on the device, once per
+    index: out[u] = the last decoded value of unit u (mod 2^32), tails
+    included.  packed / offsets / list_ptr / start0: the stream as
+    decn256v32_lists reads it with d1=True; out: int32 CUDA tensor [nunits];
+    err: optional int64 CUDA tensor [1] (-1 = clean; reported as
+    decn256v32_lists reports).  The index is not decoded into a value-sized
+    buffer.  Asynchronous: no device-to-host read."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    if out is None:
+        out = torch.empty(nunits, dtype=torch.int32, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_unit_last_workspace_size(nunits, nlists))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_lists_unit_last(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), nlists, _ptr(start0), _ptr(out),
+                                 _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out
+
+
+def lists_range_units(list_unit, unit_last, qlist, qlo, qhi, ufirst=None, ucount=None, err=None):
+    """Doc-id ranges to unit ranges: query k asks for the units of list
+    qlist[k] that can hold a value in [qlo[k], qhi[k]] (inclusive; the int32
+    tensors are read as uint32).  list_unit: int32 CUDA tensor [nlists + 1]
+    from lists_unit_base; unit_last: int32 CUDA tensor [nunits] from
+    lists_unit_last.  ufirst / ucount: int32 CUDA tensors [nq], written:
+    list-relative first unit and unit count, (0, 0) when nothing can match;
+    err: optional int64 CUDA tensor [1] (-1 = clean; k: the first query with
+    a bad list id, which gets (0, 0)).  qlist, ufirst and ucount feed
+    decn256v32_lists_units unchanged.  Asynchronous.  Returns (ufirst,
+    ucount)."""
+    import torch
+
+    nlists = list_unit.numel() - 1
+    nunits = unit_last.numel()
+    nq = qlist.numel()
+    if ufirst is None:
+        ufirst = torch.empty(nq, dtype=torch.int32, device=qlist.device)
+    if ucount is None:
+        ucount = torch.empty(nq, dtype=torch.int32, device=qlist.device)
+    _check(lib().tpf_lists_range_units(_ptr(list_unit), _ptr(unit_last), nlists, nunits, _ptr(qlist), _ptr(qlo), _ptr(qhi), nq,
+                                       _ptr(ufirst), _ptr(ucount), _ptr(err), _stream(torch)))
+    return ufirst, ucount
+
+
+def decn256v32_lists_units(packed, offsets, list_ptr, list_unit, sel, ufirst, ucount, d1=False, start0=None, unit_last=None, out=None,
+                           out_ptr=None, err=None, ws=None):
+    """Decode units [ufirst[k], ufirst[k] + ucount[k]) of list sel[k] of a
+    resident lists stream, for every k in the order given, into one dense
+    output: selection k lands at out[out_ptr[k]:out_ptr[k+1]] -- 256 values
+    per unit, n % 256 in the list's tail unit.  packed / offsets / list_ptr /
+    list_unit / sel / start0: as decn256v32_lists_select; ufirst, ucount: int32
+    CUDA tensors [nsel] (from lists_range_units, or any ranges inside the
+    lists); unit_last: the skip table of lists_unit_last, required with d1
+    (every unit starts from the table: each selected block is decoded once)
+    and ignored without.  out: int32 CUDA tensor whose numel() is the capacity
+    in values -- the work is sized by it (default: sized from the ranges, which
+    costs a device-to-host read; pass out to stay asynchronous).  out_ptr:
+    int64 CUDA tensor [nsel + 1], written; err: optional int64 CUDA tensor [1]
+    (-1 = clean).  Returns (out, out_ptr)."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nsel = sel.numel()
+    if out is None:
+        total = 0
+        if nsel and nlists > 0:
+            idx = sel.long() & 0xFFFFFFFF
+            uf, uc = ufirst.long() & 0xFFFFFFFF, ucount.long() & 0xFFFFFFFF
+            ok = idx < nlists
+            idx = idx.clamp(max=nlists - 1)
+            n = (list_ptr[idx + 1] - list_ptr[idx]).clamp(min=0)
+            units = (n + 255) // 256
+            ok = ok & (uf + uc <= units)
+            reach = (uc > 0) & (uf + uc == units) & (n % 256 != 0)
+            total = int(((256 * uc - reach * (256 - n % 256)) * ok).sum().item())
+        out = torch.empty(max(total, 1), dtype=torch.int32, device=packed.device)[:total]
+    if out_ptr is None:
+        out_ptr = torch.empty(nsel + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_p4ndec256v32_lists_units_workspace_size(nsel, out.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_p4ndec256v32_lists_units(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
+                                          int(bool(d1)), _ptr(start0), _ptr(unit_last), _ptr(sel), _ptr(ufirst), _ptr(ucount), nsel,
+                                          _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
