@@ -490,6 +490,90 @@ int tpf_p4ndec256v32_lists_units(const uint8_t *d_in, uint64_t in_bytes, const u
                                  uint64_t out_values, uint64_t *d_out_ptr /* nsel + 1 */, void *d_ws, size_t ws_bytes,
                                  uint64_t *d_err, void *stream);
 
+/* ---- intersection with a resident index --------------------------------------
+ * tpf_lists_intersect answers nq membership queries against a delta-1 lists
+ * stream: query k is the probe values d_probe[d_probe_ptr[k] ..
+ * d_probe_ptr[k+1]), tested against list j = d_qlist[k].  It returns the
+ * values that are also in list j, with where they were found.  Only the blocks
+ * a probe value lands in are decoded, and no decoded block is written to
+ * memory.  A k-term AND is the call chained k-1 times on the device: d_out and
+ * d_out_ptr of one call are d_probe and d_probe_ptr of the next.
+ *   - The index: the stream, its offsets (OFFSETS CONTRACT), d_list_ptr and
+ *     d_list_unit as tpf_p4ndec256v32_lists_units reads them with d1 != 0;
+ *     d_start0 (NULL means 0); the skip table d_unit_last
+ *     (tpf_lists_unit_last), required.
+ *   - The probe: d_probe_ptr (nq + 1 entries) is non-decreasing and need not
+ *     start at 0; probe_values is the readable length of d_probe, and nothing
+ *     outside [d_probe_ptr[0], d_probe_ptr[nq]) is read.  Empty segments are
+ *     allowed anywhere; the same list may be the target of many queries.
+ *     d_out must not overlap d_probe.
+ *   - Definition, per probe value v at index i of query k, with ua =
+ *     d_list_unit[j] and ub = d_list_unit[j+1]: u is the first unit of
+ *     [ua, ub) with d_unit_last[u] >= v; with no such unit v is a miss.  Unit u
+ *     is decoded from d_start0[j] when u == ua, else from d_unit_last[u-1], as
+ *     tpf_p4ndec256v32_lists_units decodes it.  v is a hit iff it equals one of
+ *     the unit's decoded values, at index p of the unit.  The hits of query k
+ *     go to d_out[d_out_ptr[k] .. d_out_ptr[k+1]) in probe order; d_out_pidx
+ *     (optional) gets i, the index into d_probe; d_out_tpos (optional) gets the
+ *     list-relative position 256 (u - ua) + p.  d_out_ptr[0] = 0: the output
+ *     is dense and itself a CSR array.
+ *   - For a list that ascends without wrapping mod 2^32, with a correct table,
+ *     this is exactly "v is in list j" (the precondition of
+ *     tpf_lists_range_units).  The probe need not be sorted or free of
+ *     duplicates: the lookup is per value and every occurrence of a repeated
+ *     value is reported.  A sorted probe makes the work minimal: a unit is
+ *     decoded once per run of consecutive probe values that land in it.
+ *   - Outside the precondition (a list that wraps, a wrong table) which members
+ *     are reported is unspecified, but every reported triple is true of the
+ *     decode -- the value at d_out_tpos, decoded from the table, equals v --
+ *     and every access stays in bounds: the table holds values, never indices.
+ *   - Output bounds: nothing is written at or past d_out + out_values (the same
+ *     for d_out_pidx and d_out_tpos), and nothing outside a query's slice.
+ *     d_out is only 4-byte aligned.  Hits never exceed the probe, so out_values
+ *     = probe_values always suffices.
+ *   - Cost: no kernel is sized by nlists or nunits.  Grids and the workspace
+ *     (a few words per probe value) are sized on the host from probe_values
+ *     alone.  Stream bytes are read only at units a probe value lands in;
+ *     beyond them only the d_unit_last entries the searches visit and
+ *     d_list_ptr, d_list_unit and d_start0 of targeted lists.  Ten launches
+ *     for a probe of up to 262,144 values and twelve beyond (each of the two
+ *     run scans then takes a second launch): decided on the host by
+ *     probe_values, whatever the queries.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       < nunits        the lowest SOURCE unit, among the units decoded, whose
+ *                       parse disagrees with its offsets; hits of such a unit
+ *                       are unspecified but in bounds;
+ *       nunits + k      the first query k with d_qlist[k] >= nlists,
+ *                       list_ptr[j+1] < list_ptr[j], list_unit[j+1] <
+ *                       list_unit[j], list_unit[j+1] > nunits, a unit count
+ *                       different from that of n_j, probe_ptr[k+1] <
+ *                       probe_ptr[k] or probe_ptr[k+1] > probe_values: nothing
+ *                       is written to d_out, d_out_ptr, d_out_pidx or
+ *                       d_out_tpos;
+ *       nunits + nq     the hits do not fit out_values: nothing is written to
+ *                       d_out, d_out_pidx or d_out_tpos, but d_out_ptr is
+ *                       filled completely, so d_out_ptr[nq] is what to allocate.
+ *   - TPF_EINVAL (decided before any device call): with nq non-zero a null
+ *     d_in, d_off, d_list_ptr, d_list_unit, d_unit_last, d_probe_ptr, d_qlist,
+ *     d_out_ptr or d_ws; a null d_probe or d_out while probe_values or
+ *     out_values is non-zero; ws_bytes below
+ *     tpf_lists_intersect_workspace_size(nq, probe_values); nlists, nunits, nq
+ *     or probe_values above 0x7FFFFFFF.  nq == 0 is a successful no-op that
+ *     writes d_out_ptr[0] = 0 and sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_lists_intersect_workspace_size(uint64_t nq, uint64_t probe_values);
+int tpf_lists_intersect(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                        const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                        const uint32_t *d_start0, const uint32_t *d_unit_last,
+                        const uint32_t *d_probe, uint64_t probe_values, const uint64_t *d_probe_ptr /* nq + 1 */,
+                        const uint32_t *d_qlist, uint64_t nq,
+                        uint32_t *d_out, uint64_t out_values, uint64_t *d_out_ptr /* nq + 1 */,
+                        uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
+                        void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

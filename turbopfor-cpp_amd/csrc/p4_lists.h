@@ -96,6 +96,19 @@ hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint6
                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
                               const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount, uint64_t nsel, uint32_t * out,
                               uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s);
+// membership of probe values in resident lists (p4_lists_intersect.hip;
+// DESIGN.md 4.11).  Passes: plan (one thread per query: the checks; one per
+// probe value: its query, then its unit by a search over the skip table) ->
+// item heads and their run scan -> items (runs of probe values with one list
+// and one unit) -> full blocks -> tails (each item's unit decoded into LDS and
+// searched, never stored) -> hit flags and their run scan -> compaction
+// (d_out_ptr, the verdict, the scatter).  Sized by nq and probe_values alone.
+size_t lists_intersect_workspace(uint64_t nq, uint64_t probe_values);
+hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                                  const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
+                                  const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
+                                  uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
+                                  uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

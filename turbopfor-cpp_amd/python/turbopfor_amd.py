@@ -160,6 +160,13 @@ def lib():
             L.tpf_p4ndec256v32_lists_units.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
                                                        c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_p4ndec256v32_lists_units.restype = ctypes.c_int
+        # the intersection with a resident index: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_lists_intersect"):
+            L.tpf_lists_intersect_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_lists_intersect_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_intersect.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
+                                              c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_intersect.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -739,4 +746,42 @@ def decn256v32_lists_units(packed, offsets, list_ptr, list_unit, sel, ufirst, uc
     _check(L.tpf_p4ndec256v32_lists_units(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
                                           int(bool(d1)), _ptr(start0), _ptr(unit_last), _ptr(sel), _ptr(ufirst), _ptr(ucount), nsel,
                                           _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
+
+
+# ---- intersection with a resident index (include/turbopfor_gpu.h tpf_lists_intersect) ----
+def lists_intersect(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0=None, out=None, out_ptr=None,
+                    pidx=None, tpos=None, err=None, ws=None):
+    """Which probe doc ids are in their target lists: query k is the values
+    probe[probe_ptr[k]:probe_ptr[k+1]] (int32 CUDA tensor read as uint32,
+    sorted for the least work; probe_ptr: int64 CUDA tensor [nq + 1],
+    non-decreasing) tested against list qlist[k] (int32 CUDA tensor [nq]) of a
+    resident delta-1 lists stream.  packed / offsets / list_ptr / list_unit /
+    start0: as decn256v32_lists_units with d1=True; unit_last: the skip table
+    of lists_unit_last.  The hits of query k land at
+    out[out_ptr[k]:out_ptr[k+1]] in probe order, so (out, out_ptr) is the
+    probe of the next call of a k-term AND.  Only the blocks a probe value
+    lands in are decoded, and none is written to memory.  out: int32 CUDA
+    tensor whose numel() is the capacity in values (default: probe.numel(),
+    which always suffices, so the default stays asynchronous); out_ptr: int64
+    CUDA tensor [nq + 1], written; pidx / tpos: optional int32 CUDA tensors of
+    out's capacity, written when passed: the hit's index into probe and its
+    position in the target list; err: optional int64 CUDA tensor [1] (-1 =
+    clean).  Returns (out, out_ptr)."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nq = qlist.numel()
+    if out is None:
+        out = torch.empty(probe.numel(), dtype=torch.int32, device=packed.device)
+    if out_ptr is None:
+        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_intersect_workspace_size(nq, probe.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_lists_intersect(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
+                                 _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
+                                 out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
