@@ -457,6 +457,164 @@ static void gen64_short(Writer & w, uint64_t seed, bool v128)
     }
 }
 
+// ------------------------------------------------- horizontal 64-bit (p4Enc64)
+// The base and the patch bits hold n values (any n <= 256), so n is swept
+// over the bitmap-word and byte boundaries.  The encoder stores 8 bytes at a
+// time (bitmap words, the constant): enc has slack behind the block.
+static void add64h(Writer & w, const std::vector<uint64_t> & v, bool d1, uint64_t start)
+{
+    const unsigned n = static_cast<unsigned>(v.size());
+    std::vector<uint8_t> enc(n * 10 + 4096, 0);
+    std::vector<uint64_t> in(256 + 64, 0);
+    std::copy(v.begin(), v.end(), in.begin());
+    uint8_t * e = d1 ? sc::p4D1Enc64(in.data(), n, enc.data(), start) : sc::p4Enc64(in.data(), n, enc.data());
+    const uint32_t len = static_cast<uint32_t>(e - enc.data());
+    std::vector<uint64_t> dec(256 + 64, 0);
+    const uint8_t * rp = d1 ? sc::p4D1Dec64(enc.data(), n, dec.data(), start) : sc::p4Dec64(enc.data(), n, dec.data());
+    if (rp != e)
+        die("64h decode end pointer", w.count);
+    if (std::memcmp(dec.data(), v.data(), n * 8u) != 0)
+        die("64h round trip", w.count);
+    w.record(d1 ? 1u : 0u, n, start, 8u, v.data(), enc.data(), len);
+}
+
+static uint64_t ofWidth(Rng & r, unsigned b) // a value of width exactly b (b >= 1)
+{
+    return (1ull << (b - 1)) | (b > 1 ? r.range(0, (1ull << (b - 1)) - 1ull) : 0ull);
+}
+
+static void gen64h(Writer & w, uint64_t seed)
+{
+    Rng r(seed);
+    const std::vector<unsigned> ns = {1, 2, 63, 64, 65, 127, 128, 129, 255, 256};
+    const std::vector<unsigned> wide_ns = {63, 64, 65, 127, 128, 129, 255, 256};
+    unsigned rot = 0;
+    auto next_n = [&] { return wide_ns[rot++ % wide_ns.size()]; };
+
+    for (unsigned n : ns)
+    {
+        std::vector<uint64_t> v(n, 0ull);
+        add64h(w, v, false, 0); // all zero: the header byte only
+        // random of width <= b: every width at n = 256 and n <= 2, a thinner set between
+        for (unsigned b = 1; b <= 64; ++b)
+        {
+            const bool thin = b == 1 || b == 7 || b == 8 || b == 31 || b == 32 || b == 33 || b == 57 || b == 63 || b == 64;
+            if (n != 256 && n > 2 && !thin)
+                continue;
+            for (auto & x : v)
+                x = r.range(0, b == 64 ? ~0ull : ((1ull << b) - 1ull));
+            v[r.range(0, n - 1)] = ofWidth(r, b);
+            add64h(w, v, false, 0);
+        }
+    }
+    // constants: 8-byte store, advance ceil(b/8); header 63 stands for 63 and 64
+    for (unsigned n : {1u, 2u, 65u, 256u})
+        for (unsigned b : {1u, 8u, 32u, 33u, 56u, 57u, 63u, 64u})
+        {
+            std::vector<uint64_t> v(n, ofWidth(r, b));
+            add64h(w, v, false, 0);
+        }
+    // exceptions reaching bit `hi` over a base of width bw
+    for (unsigned bw : {0u, 3u, 8u, 20u, 31u, 32u, 33u, 40u})
+        for (unsigned hi : {33u, 48u, 62u, 63u, 64u})
+            for (unsigned pct : {2u, 10u, 30u})
+            {
+                if (hi <= bw)
+                    continue;
+                std::vector<uint64_t> v(next_n());
+                bool any = false;
+                for (auto & x : v)
+                {
+                    const bool ex = r.range(0, 99) < pct;
+                    any |= ex;
+                    x = ex ? r.range(1ull << (hi - 1), hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) : (bw ? r.range(0, (1ull << bw) - 1ull) : 0ull);
+                }
+                if (!any)
+                    v[r.range(0, v.size() - 1)] = ofWidth(r, hi);
+                add64h(w, v, false, 0);
+            }
+    // mixed exceptions: many one-byte vbyte markers and a few long forms, so the
+    // compressed vbEnc64 stream is chosen and carries every marker length
+    unsigned wstep = 0;
+    for (unsigned rep = 0; rep < 32; ++rep)
+    {
+        const unsigned n = next_n();
+        const unsigned b = static_cast<unsigned>(r.range(0, 11));
+        std::vector<uint64_t> v(n);
+        for (auto & x : v)
+            x = b ? r.range(0, (1ull << b) - 1ull) : 0ull;
+        const unsigned xn = static_cast<unsigned>(r.range((n + 7) / 8, n / 3));
+        std::vector<unsigned> pos(n);
+        for (unsigned i = 0; i < n; ++i)
+            pos[i] = i;
+        for (unsigned i = 0; i < xn; ++i)
+            std::swap(pos[i], pos[i + r.range(0, n - 1 - i)]);
+        for (unsigned i = 0; i < xn; ++i)
+            v[pos[i]] |= r.range(1, 149) << b;
+        const unsigned big = static_cast<unsigned>(r.range(1, 3));
+        for (unsigned i = 0; i < big; ++i)
+        {
+            const unsigned span = 64u - (b + 8u) + 1u;
+            v[pos[i]] = ofWidth(r, b + 8u + (wstep * 5u) % span);
+            ++wstep;
+        }
+        add64h(w, v, false, 0);
+    }
+    // maximum width exactly 63: the plan turns b = 63 into 64 / bx = 0
+    for (unsigned n : {65u, 256u})
+    {
+        std::vector<uint64_t> v(n);
+        for (auto & x : v)
+            x = r.range(1ull << 62, (1ull << 63) - 1ull);
+        add64h(w, v, false, 0);
+        for (auto & x : v)
+            x = r.range(0, (1ull << 20) - 1ull);
+        v[r.range(0, n - 1)] = (1ull << 62) | 5ull; // a single top value
+        add64h(w, v, false, 0);
+        for (auto & x : v)
+            x = r.range(0, (1ull << 62) - 1ull);
+        v[r.range(0, n - 1)] = (1ull << 62) | 5ull;
+        add64h(w, v, false, 0);
+    }
+    // delta-1: gaps up to 2^62 (the sums wrap), starts 0, near 2^32 and wrapping 2^64
+    for (uint64_t md : {1ull, 255ull, 65535ull, (1ull << 40), (1ull << 62)})
+        for (uint64_t st : {0ull, 0xFFFFF000ull, ~0ull - 1000ull})
+        {
+            std::vector<uint64_t> v(md == 1ull ? 256u : next_n());
+            uint64_t cur = st;
+            for (auto & x : v)
+                x = (cur += r.range(1, md));
+            add64h(w, v, true, st);
+        }
+    for (unsigned n : {1u, 2u})
+        for (uint64_t st : {0ull, ~0ull - 1000ull})
+        {
+            std::vector<uint64_t> v(n);
+            uint64_t cur = st;
+            for (auto & x : v)
+                x = (cur += r.range(1, 1ull << 33));
+            add64h(w, v, true, st);
+        }
+    // decode-only: header 0x80 | b with bx == 0 (p4dec64.cpp:95), b = 8 and 63 (= 64)
+    for (unsigned b : {8u, 63u})
+        for (unsigned n : {65u, 256u})
+        {
+            const unsigned bits = b == 63u ? 64u : b;
+            std::vector<uint8_t> enc(2 + n * 8 + 64, 0);
+            enc[0] = static_cast<uint8_t>(0x80u | b);
+            enc[1] = 0;
+            for (unsigned i = 0; i < (n * bits + 7u) / 8u; ++i)
+                enc[2 + i] = static_cast<uint8_t>(r.next());
+            std::vector<uint64_t> dec(256 + 64);
+            const uint8_t * e = sc::p4Dec64(enc.data(), n, dec.data());
+            if (e != enc.data() + 2 + (n * bits + 7u) / 8u)
+                die("64h decode-only end pointer", w.count);
+            w.record(2u, n, 0, 8u, dec.data(), enc.data(), static_cast<uint32_t>(e - enc.data()));
+            const uint8_t * e1 = sc::p4D1Dec64(enc.data(), n, dec.data(), ~0ull - 77ull);
+            w.record(3u, n, ~0ull - 77ull, 8u, dec.data(), enc.data(), static_cast<uint32_t>(e1 - enc.data()));
+        }
+}
+
 // Hand-made decode-only vectors: valid streams the encoder never emits.
 static void genDecodeOnly(Writer & w)
 {
@@ -504,6 +662,11 @@ int main(int argc, char ** argv)
         gen64(w, 0x128064, true);
         gen64_short(w, 0x128065, true);
         w.save(dir + "/g128v64.bin");
+    }
+    {
+        Writer w;
+        gen64h(w, 0x64);
+        w.save(dir + "/g64.bin");
     }
     return 0;
 }

@@ -87,7 +87,11 @@ extern "C" {
     W64ENC(prefix##p4enc256v64, ns, p4Enc256v64)             \
     W64D1ENC(prefix##p4d1enc256v64, ns, p4D1Enc256v64)       \
     W64DEC(prefix##p4dec256v64, ns, p4Dec256v64)             \
-    W64D1DEC(prefix##p4d1dec256v64, ns, p4D1Dec256v64)
+    W64D1DEC(prefix##p4d1dec256v64, ns, p4D1Dec256v64)       \
+    W64ENC(prefix##p4enc64, ns, p4Enc64)                     \
+    W64D1ENC(prefix##p4d1enc64, ns, p4D1Enc64)               \
+    W64DEC(prefix##p4dec64, ns, p4Dec64)                     \
+    W64D1DEC(prefix##p4d1dec64, ns, p4D1Dec64)
 
 FAMILY(tpref_s_, turbopfor::scalar)
 FAMILY(tpref_d_, turbopfor)

@@ -783,6 +783,135 @@ const uint8_t *orc_p4d1dec256v64(const uint8_t *in, unsigned n, uint64_t *out, u
     return in;
 }
 
+/* ------------------------------------------- horizontal 64-bit codec (64) */
+
+/* p4Enc64 -- p4enc64.cpp:129-145, payload :94-118, exceptions :12-91.
+ * The base holds n values (not the layout width), horizontally, and so do
+ * the bitmap patch bits.  The constant block stores 8 bytes and advances
+ * ceil(b/8) (:112-113); only the counted bytes are written here. */
+uint8_t *orc_p4enc64(const uint64_t *in, unsigned n, uint8_t *out)
+{
+    if (n == 0u) return out;
+    unsigned bx;
+    unsigned b = orc_p4bits64(in, n, &bx);
+    out = write_header(out, b, bx, 64u);
+    if (bx == 0u) return hpack(in, n, out, b); /* b == 0: all zero, header only */
+    if (bx == 66u) {
+        for (unsigned i = 0; i < (b + 7u) / 8u; ++i) out[i] = (uint8_t)(in[0] >> (8u * i));
+        return out + (b + 7u) / 8u;
+    }
+    const uint64_t bmask = mask64(b);
+    uint64_t base[256], exc[256];
+    unsigned pos[256], xn = 0;
+    for (unsigned i = 0; i < n; ++i) {
+        base[i] = in[i] & bmask;
+        if (in[i] > bmask) {
+            pos[xn] = i;
+            exc[xn] = in[i] >> b;
+            ++xn;
+        }
+    }
+    if (bx <= 64u) {
+        uint8_t bm[32];
+        memset(bm, 0, sizeof(bm));
+        for (unsigned k = 0; k < xn; ++k) bm[pos[k] >> 3] |= (uint8_t)(1u << (pos[k] & 7u));
+        memcpy(out, bm, pad8(n));
+        out += pad8(n);
+        out = hpack(exc, xn, out, bx);
+        return hpack(base, n, out, b);
+    }
+    *out++ = (uint8_t)xn;
+    out = hpack(base, n, out, b);
+    out = vbenc64(exc, xn, out);
+    for (unsigned k = 0; k < xn; ++k) *out++ = (uint8_t)pos[k];
+    return out;
+}
+
+/* p4Dec64 -- p4dec64.cpp:70-141, bitmap exceptions :10-66.  The constant
+ * block loads 8 bytes and masks (:110-112); only the counted bytes are read
+ * here, which gives the same value. */
+const uint8_t *orc_p4dec64(const uint8_t *in, unsigned n, uint64_t *out)
+{
+    if (n == 0u) return in;
+    const uint8_t *ip = in;
+    unsigned b = *ip++;
+    if ((b & 0xC0u) == 0xC0u) { /* :101-118 */
+        b &= 0x3Fu;
+        if (b == 63u) b = 64u;
+        unsigned nbytes = (b + 7u) / 8u;
+        uint64_t v = 0;
+        for (unsigned i = 0; i < nbytes; ++i) v |= (uint64_t)ip[i] << (8u * i);
+        v &= mask64(b);
+        for (unsigned i = 0; i < n; ++i) out[i] = v;
+        return ip + nbytes;
+    }
+    if ((b & 0x40u) == 0u) { /* plain :80-85, bitmap :87-99 (bx == 0 accepted at :95) */
+        unsigned bx = 0;
+        if (b & 0x80u) {
+            bx = *ip++;
+            b &= 0x7Fu;
+        }
+        if (b == 63u) b = 64u;
+        if (bx == 0u) return hunpack(ip, n, out, b);
+        if (bx > 64u) bx = 64u; /* malformed (the reference's unpack is undefined there): clamped as the GPU decoders do */
+        uint64_t bm[4] = {0, 0, 0, 0};
+        unsigned words = (n + 63u) / 64u, xn = 0;
+        for (unsigned w = 0; w < words; ++w) {
+            uint64_t word = 0;
+            unsigned have = pad8(n) - 8u * w; /* the reference loads 8 bytes and masks: same bits */
+            for (unsigned i = 0; i < 8u && i < have; ++i) word |= (uint64_t)ip[8u * w + i] << (8u * i);
+            if (w == words - 1u && (n & 63u)) word &= (1ull << (n & 63u)) - 1ull;
+            bm[w] = word;
+            xn += (unsigned)__builtin_popcountll(word);
+        }
+        ip += pad8(n);
+        uint64_t exc[256];
+        ip = hunpack(ip, xn, exc, bx);
+        ip = hunpack(ip, n, out, b);
+        unsigned k = 0;
+        for (unsigned w = 0; w < words; ++w) {
+            uint64_t word = bm[w];
+            while (word) {
+                unsigned bit = (unsigned)__builtin_ctzll(word);
+                out[w * 64u + bit] |= shl64u(exc[k++], b);
+                word &= word - 1ull;
+            }
+        }
+        return ip;
+    }
+    b &= 0x3Fu; /* vbyte :120-140 */
+    if (b == 63u) b = 64u;
+    unsigned xn = *ip++;
+    ip = hunpack(ip, n, out, b);
+    uint64_t exc[256 + 64];
+    ip = vbdec64(ip, xn, exc);
+    for (unsigned k = 0; k < xn; ++k)
+        if (ip[k] < n) out[ip[k]] |= shl64u(exc[k], b); /* a position >= n is malformed; skipped so a short out[] stays in bounds */
+    return ip + xn;
+}
+
+/* p4D1Enc64 -- p4d1enc64.cpp:7-15 */
+uint8_t *orc_p4d1enc64(const uint64_t *in, unsigned n, uint8_t *out, uint64_t start)
+{
+    if (n == 0u) return out;
+    uint64_t t[256 + 8];
+    for (unsigned i = 0; i < n; ++i) {
+        t[i] = in[i] - start - 1u;
+        start = in[i];
+    }
+    return orc_p4enc64(t, n, out);
+}
+
+/* p4D1Dec64 -- p4d1dec64.cpp:97-193: the same parse as p4Dec64 with the
+ * delta-1 prefix sum applied at the end of every branch. */
+const uint8_t *orc_p4d1dec64(const uint8_t *in, unsigned n, uint64_t *out, uint64_t start)
+{
+    if (n == 0u) return in;
+    const uint8_t *r = orc_p4dec64(in, n, out);
+    delta1_64(out, n, start);
+    return r;
+}
+
 /* ---------------------------------------------------------- batch helpers */
 
 uint64_t orc_enc256v32_batch(const uint32_t *in, uint64_t nb, uint8_t *out, uint64_t *off)
@@ -900,6 +1029,46 @@ int orc_d1dec32_batch(const uint8_t *in, const uint64_t *off, uint64_t nb, unsig
 {
     for (uint64_t i = 0; i < nb; ++i) {
         const uint8_t *e = orc_p4d1dec32(in + off[i], bn, out + i * bn, st[i]);
+        if ((uint64_t)(e - in) != off[i + 1]) return -1 - (int)(i & 0x3fffffff);
+    }
+    return 0;
+}
+
+uint64_t orc_enc64_batch(const uint64_t *in, uint64_t nb, unsigned bn, uint8_t *out, uint64_t *off)
+{
+    uint8_t *op = out;
+    for (uint64_t i = 0; i < nb; ++i) {
+        off[i] = (uint64_t)(op - out);
+        op = orc_p4enc64(in + i * bn, bn, op);
+    }
+    off[nb] = (uint64_t)(op - out);
+    return off[nb];
+}
+
+uint64_t orc_d1enc64_batch(const uint64_t *in, uint64_t nb, unsigned bn, uint8_t *out, uint64_t *off, const uint64_t *st)
+{
+    uint8_t *op = out;
+    for (uint64_t i = 0; i < nb; ++i) {
+        off[i] = (uint64_t)(op - out);
+        op = orc_p4d1enc64(in + i * bn, bn, op, st[i]);
+    }
+    off[nb] = (uint64_t)(op - out);
+    return off[nb];
+}
+
+int orc_dec64_batch(const uint8_t *in, const uint64_t *off, uint64_t nb, unsigned bn, uint64_t *out)
+{
+    for (uint64_t i = 0; i < nb; ++i) {
+        const uint8_t *e = orc_p4dec64(in + off[i], bn, out + i * bn);
+        if ((uint64_t)(e - in) != off[i + 1]) return -1 - (int)(i & 0x3fffffff);
+    }
+    return 0;
+}
+
+int orc_d1dec64_batch(const uint8_t *in, const uint64_t *off, uint64_t nb, unsigned bn, uint64_t *out, const uint64_t *st)
+{
+    for (uint64_t i = 0; i < nb; ++i) {
+        const uint8_t *e = orc_p4d1dec64(in + off[i], bn, out + i * bn, st[i]);
         if ((uint64_t)(e - in) != off[i + 1]) return -1 - (int)(i & 0x3fffffff);
     }
     return 0;

@@ -19,6 +19,8 @@
  *   128v64 : hybrid (128v32 of pair-swapped low halves if b<=32, horizontal
  *            64-bit stream if b>32)          (bitpack128v64_scalar.cpp:38-104)
  *   256v64 : two consecutive 128v64 blocks    (p4enc256v64_scalar.cpp:15-30)
+ *   64     : horizontal LSB-first bitstream of n 64-bit values, in the base
+ *            and in the bitmap patch bits     (p4enc64.cpp:12-145, p4dec64.cpp:10-141)
  */
 #ifndef TPF_ORACLE_H
 #define TPF_ORACLE_H
@@ -56,6 +58,11 @@ uint8_t *orc_p4d1enc256v64(const uint64_t *in, unsigned n, uint8_t *out, uint64_
 const uint8_t *orc_p4dec256v64(const uint8_t *in, unsigned n, uint64_t *out);
 const uint8_t *orc_p4d1dec256v64(const uint8_t *in, unsigned n, uint64_t *out, uint64_t start);
 
+uint8_t *orc_p4enc64(const uint64_t *in, unsigned n, uint8_t *out);
+uint8_t *orc_p4d1enc64(const uint64_t *in, unsigned n, uint8_t *out, uint64_t start);
+const uint8_t *orc_p4dec64(const uint8_t *in, unsigned n, uint64_t *out);
+const uint8_t *orc_p4d1dec64(const uint8_t *in, unsigned n, uint64_t *out, uint64_t start);
+
 /* p4Bits32 / p4Bits64 cost model (p4_scalar_internal.cpp:270-387, :538-652) */
 unsigned orc_p4bits32(const uint32_t *in, unsigned n, unsigned *bx);
 unsigned orc_p4bits64(const uint64_t *in, unsigned n, unsigned *bx);
@@ -80,6 +87,12 @@ uint64_t orc_d1enc32_batch(const uint32_t *in, uint64_t nblocks, unsigned blk_n,
                            const uint32_t *starts);
 int orc_d1dec32_batch(const uint8_t *in, const uint64_t *off, uint64_t nblocks, unsigned blk_n, uint32_t *out,
                       const uint32_t *starts);
+uint64_t orc_enc64_batch(const uint64_t *in, uint64_t nblocks, unsigned blk_n, uint8_t *out, uint64_t *off);
+int orc_dec64_batch(const uint8_t *in, const uint64_t *off, uint64_t nblocks, unsigned blk_n, uint64_t *out);
+uint64_t orc_d1enc64_batch(const uint64_t *in, uint64_t nblocks, unsigned blk_n, uint8_t *out, uint64_t *off,
+                           const uint64_t *starts);
+int orc_d1dec64_batch(const uint8_t *in, const uint64_t *off, uint64_t nblocks, unsigned blk_n, uint64_t *out,
+                      const uint64_t *starts);
 
 /* Multi-threaded streaming decode used by bench.py's cpu_baseline leg
  * (kind "port"): nthreads workers each decode a contiguous block range. */

@@ -32,6 +32,7 @@ def lib():
             ("orc_p4enc128v64", [u64p, c_u, u8p]), ("orc_p4enc256v64", [u64p, c_u, u8p]),
             ("orc_p4d1enc128v64", [u64p, c_u, u8p, ctypes.c_uint64]),
             ("orc_p4d1enc256v64", [u64p, c_u, u8p, ctypes.c_uint64]),
+            ("orc_p4enc64", [u64p, c_u, u8p]), ("orc_p4d1enc64", [u64p, c_u, u8p, ctypes.c_uint64]),
         ]:
             f = getattr(L, name)
             f.argtypes = argt
@@ -45,6 +46,7 @@ def lib():
             ("orc_p4dec128v64", [u8p, c_u, u64p]), ("orc_p4dec256v64", [u8p, c_u, u64p]),
             ("orc_p4d1dec128v64", [u8p, c_u, u64p, ctypes.c_uint64]),
             ("orc_p4d1dec256v64", [u8p, c_u, u64p, ctypes.c_uint64]),
+            ("orc_p4dec64", [u8p, c_u, u64p]), ("orc_p4d1dec64", [u8p, c_u, u64p, ctypes.c_uint64]),
         ]:
             f = getattr(L, name)
             f.argtypes = argt
@@ -68,6 +70,12 @@ def lib():
         L.orc_d1enc32_batch.restype = ctypes.c_uint64
         L.orc_dec32_batch.argtypes = [u8p, u64p, ctypes.c_uint64, c_u, u32p]
         L.orc_d1dec32_batch.argtypes = [u8p, u64p, ctypes.c_uint64, c_u, u32p, u32p]
+        L.orc_enc64_batch.argtypes = [u64p, ctypes.c_uint64, c_u, u8p, u64p]
+        L.orc_enc64_batch.restype = ctypes.c_uint64
+        L.orc_d1enc64_batch.argtypes = [u64p, ctypes.c_uint64, c_u, u8p, u64p, u64p]
+        L.orc_d1enc64_batch.restype = ctypes.c_uint64
+        L.orc_dec64_batch.argtypes = [u8p, u64p, ctypes.c_uint64, c_u, u64p]
+        L.orc_d1dec64_batch.argtypes = [u8p, u64p, ctypes.c_uint64, c_u, u64p, u64p]
         L.orc_dec256v32_batch_mt.argtypes = [u8p, u64p, ctypes.c_uint64, u32p, ctypes.c_int]
         L.orc_p4bits32.argtypes = [u32p, c_u, ctypes.POINTER(c_u)]
         L.orc_p4bits32.restype = c_u
@@ -84,7 +92,7 @@ def ptr(a, t):
 # --- per-block convenience (return python bytes / numpy) --------------------
 _FMT = {
     "256v32": (np.uint32, 256), "128v32": (np.uint32, 128), "32": (np.uint32, None),
-    "128v64": (np.uint64, 128), "256v64": (np.uint64, 256),
+    "128v64": (np.uint64, 128), "256v64": (np.uint64, 256), "64": (np.uint64, None),
 }
 
 
@@ -202,6 +210,36 @@ def dec32_batch(packed, off, nb, bn, starts=None):
     else:
         st = np.ascontiguousarray(starts, dtype=np.uint32)
         rc = L.orc_d1dec32_batch(ptr(src, u8p), ptr(off, u64p), nb, bn, ptr(out, u32p), ptr(st, u32p))
+    assert rc == 0, rc
+    return out
+
+
+def enc64_batch(vals2d, starts=None):
+    """vals2d: (nblocks, n) uint64, one p4Enc64 / p4D1Enc64 block per row."""
+    v = np.ascontiguousarray(vals2d, dtype=np.uint64)
+    nb, bn = v.shape
+    out = np.zeros(nb * (bn * 8 + 8) + 4096, dtype=np.uint8)
+    off = np.zeros(nb + 1, dtype=np.uint64)
+    L = lib()
+    if starts is None:
+        tot = L.orc_enc64_batch(ptr(v, u64p), nb, bn, ptr(out, u8p), ptr(off, u64p))
+    else:
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        tot = L.orc_d1enc64_batch(ptr(v, u64p), nb, bn, ptr(out, u8p), ptr(off, u64p), ptr(st, u64p))
+    return out[:tot].copy(), off
+
+
+def dec64_batch(packed, off, nb, bn, starts=None):
+    src = np.zeros(len(packed) + 64, dtype=np.uint8)
+    src[: len(packed)] = packed
+    out = np.zeros((nb, bn), dtype=np.uint64)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    L = lib()
+    if starts is None:
+        rc = L.orc_dec64_batch(ptr(src, u8p), ptr(off, u64p), nb, bn, ptr(out, u64p))
+    else:
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        rc = L.orc_d1dec64_batch(ptr(src, u8p), ptr(off, u64p), nb, bn, ptr(out, u64p), ptr(st, u64p))
     assert rc == 0, rc
     return out
 

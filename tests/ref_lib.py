@@ -25,7 +25,10 @@ def lib():
         for fam in ("tpref_s_", "tpref_d_"):
             for fmt, ip, vp in (("256v32", u32p, ctypes.c_uint32), ("128v32", u32p, ctypes.c_uint32),
                                 ("32", u32p, ctypes.c_uint32), ("256v64", u64p, ctypes.c_uint64),
-                                ("128v64", u64p, ctypes.c_uint64)):
+                                ("128v64", u64p, ctypes.c_uint64), ("64", u64p, ctypes.c_uint64)):
+                # the p4*64 wrappers are absent from a libtpref.so built before ref_shim.cpp exported them
+                if fmt == "64" and not hasattr(L, fam + "p4enc64"):
+                    continue
                 f = getattr(L, fam + "p4enc" + fmt)
                 f.argtypes = [ip, ctypes.c_uint, u8p]
                 f.restype = ctypes.c_void_p

@@ -12,7 +12,9 @@ import ctypes
 import numpy as np
 import pytest
 
+import h64_inputs
 import oracle_lib
+import p4_modes
 
 torch = pytest.importorskip("torch")
 tpf = pytest.importorskip("turbopfor_amd")
@@ -70,6 +72,29 @@ def test_chained64_vs_oracle_sequential(fmt, nu):
     torch.cuda.synchronize()
     assert int(err.item()) == -1
     np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), exp)
+
+
+@pytest.mark.parametrize("fmt", ["256v64", "128v64"])
+def test_chained64_compressed_vbyte(fmt):
+    """300 units whose gaps are the compressed-vbyte inputs of
+    test_gpu_formats.py::test_wide_vbyte_compressed_every_marker_form (many
+    one-byte markers and every long form): the sums pass (k_dsum128v64_lanes)
+    and the decode pass (k_dec128v64w) both parse the compressed stream through
+    vbyte_exceptions_g<true, 128>.  Against the input values."""
+    nu, width, start0 = 300, (256 if fmt == "256v64" else 128), (1 << 64) - 12345
+    gaps = h64_inputs.wide_vbyte_gaps("256v64", 256, nu).reshape(-1, width)[:nu]
+    vals, starts = h64_inputs.d1_list(gaps, start0)
+    encs = [oracle_lib.encode(fmt, vals[i], d1=True, start=int(starts[i])) for i in range(nu)]
+    packed_np = np.frombuffer(b"".join(encs), dtype=np.uint8).copy()
+    offs_np = np.concatenate([[0], np.cumsum([len(e) for e in encs])]).astype(np.int64)
+    modes, lens = p4_modes.census64(packed_np, offs_np, 128, halves=width // 128, base_n=128)
+    assert 2 * modes["vb_comp"] >= nu * (width // 128), dict(modes)
+    assert all(lens[k] >= 10 for k in range(1, 10)), sorted(lens.items())
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    out = tpf.dec64_chained(fmt, torch.from_numpy(packed_np).to(DEV), torch.from_numpy(offs_np).to(DEV), nu, start0=start0, err=err)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), vals)
 
 
 def test_chained64_shards_exchange_totals():

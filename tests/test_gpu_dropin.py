@@ -19,7 +19,7 @@ tpf = pytest.importorskip("turbopfor_amd")
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"32": "32", "128v32": "128v32", "256v32": "256v32", "128v64": "128v64", "256v64": "256v64"}
+NAMES = {"32": "32", "128v32": "128v32", "256v32": "256v32", "64": "64", "128v64": "128v64", "256v64": "256v64"}
 
 
 def capi():
@@ -42,10 +42,10 @@ def perblock_mode(request):
 
 
 @pytest.mark.parametrize("fname,fmt", [("g32.bin", "32"), ("g128v32.bin", "128v32"), ("g256v32.bin", "256v32"),
-                                       ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64")])
+                                       ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64")])
 def test_per_block_mirrors_match_golden(fname, fmt, perblock_mode):
     L = capi()
-    wide = fmt in ("128v64", "256v64")
+    wide = fmt in ("64", "128v64", "256v64")
     dt = np.uint64 if wide else np.uint32
     vt = ctypes.c_uint64 if wide else ctypes.c_uint32
     recs = golden_io.load(fname)
@@ -139,6 +139,50 @@ def test_host_streams_vs_oracle(chunk_bytes, monkeypatch):
                         starts.ctypes.data)
     assert rc == 0, L.tpf_last_error()
     np.testing.assert_array_equal(back2, vals)
+
+
+def test_host_streams_p4enc64_vs_oracle():
+    """tpf_host_enc / tpf_host_dec on the horizontal 64-bit format (fmt 3),
+    n = 127, 3,000 blocks of every mode: offsets scanned by the host framing
+    (h_off = NULL on decode), bytes and values against the oracle."""
+    import h64_inputs
+
+    L = capi()
+    L.tpf_host_dec.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                               ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    L.tpf_host_enc.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_int,
+                               ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    L.tpf_enc_bound.restype = ctypes.c_uint64
+    L.tpf_enc_bound.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint]
+    nb, n = 3000, 127
+    vals = h64_inputs.h64_values(np.random.default_rng(64127), nb, n)
+    exp_packed, exp_off = oracle_lib.enc64_batch(vals)
+    cap = int(L.tpf_enc_bound(3, nb, n))
+    out = np.zeros(cap, dtype=np.uint8)
+    off = np.zeros(nb + 1, dtype=np.uint64)
+    rc = L.tpf_host_enc(3, vals.ctypes.data, nb, n, 0, None, 0, out.ctypes.data, cap, off.ctypes.data)
+    assert rc == 0, L.tpf_last_error()
+    np.testing.assert_array_equal(off, exp_off)
+    np.testing.assert_array_equal(out[: off[-1]], exp_packed)
+    for h_off in (None, exp_off.ctypes.data):
+        back = np.zeros_like(vals)
+        rc = L.tpf_host_dec(3, exp_packed.ctypes.data, len(exp_packed), h_off, nb, n, back.ctypes.data, None)
+        assert rc == 0, L.tpf_last_error()
+        np.testing.assert_array_equal(back, vals)
+    # delta-1, one chained list (wraps 2^64) and per-unit starts
+    x, starts = h64_inputs.d1_list(vals, (1 << 64) - 99)
+    exp_p, exp_o = oracle_lib.enc64_batch(x, starts=starts)
+    for st, s0 in ((None, (1 << 64) - 99), (starts, 0)):
+        out.fill(0)
+        rc = L.tpf_host_enc(3, x.ctypes.data, nb, n, 1, None if st is None else st.ctypes.data, s0, out.ctypes.data, cap,
+                            off.ctypes.data)
+        assert rc == 0, L.tpf_last_error()
+        np.testing.assert_array_equal(off, exp_o)
+        np.testing.assert_array_equal(out[: off[-1]], exp_p)
+    back = np.zeros_like(x)
+    rc = L.tpf_host_dec(3, exp_p.ctypes.data, len(exp_p), exp_o.ctypes.data, nb, n, back.ctypes.data, starts.ctypes.data)
+    assert rc == 0, L.tpf_last_error()
+    np.testing.assert_array_equal(back, x)
 
 
 @pytest.mark.parametrize("down", ["sdma", "kernel"])

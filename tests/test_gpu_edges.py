@@ -250,3 +250,17 @@ def test_out_of_format_widths_reported():
     torch.cuda.synchronize()
     assert int(err.item()) == 3
     np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32).reshape(4, 127)[:3], g32)
+    # p4Dec64 bitmap block whose bx byte is 70 (> 64): 2 + 16 bitmap bytes (no bit set) + pad8(127 * 5) base bytes
+    g64 = rng.integers(0, 1 << 40, size=(3, 127), dtype=np.uint64)
+    p64, o64 = oracle_lib.enc64_batch(g64)
+    blk = bytes([0x80 | 5, 70]) + bytes(16) + bytes((127 * 5 + 7) // 8)
+    stream = np.concatenate([p64, np.frombuffer(blk, np.uint8)])
+    offs = np.concatenate([o64, [o64[-1] + len(blk)]]).astype(np.int64)
+    scanned = np.zeros(5, dtype=np.uint64)
+    assert L.tpf_scan_offsets(3, ctypes.c_void_p(stream.ctypes.data), ctypes.c_uint64(len(stream)), 127, ctypes.c_uint64(4),
+                              ctypes.c_void_p(scanned.ctypes.data)) < 0
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    out = tpf.dec_batch("64", torch.from_numpy(stream).to(DEV), torch.from_numpy(offs).to(DEV), 4, 127, err=err)
+    torch.cuda.synchronize()
+    assert int(err.item()) == 3
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64).reshape(4, 127)[:3], g64)

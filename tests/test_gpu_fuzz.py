@@ -79,7 +79,8 @@ def test_fuzz_256v32_plain_d1_chained(seed):
     assert np.array_equal(oc.cpu().numpy().view(np.uint32)[:first1], pv[:first1])
 
 
-@pytest.mark.parametrize("fmt,n", [("32", 127), ("128v32", 128), ("256v64", 256), ("128v64", 100)])
+@pytest.mark.parametrize("fmt,n", [("32", 127), ("128v32", 128), ("256v64", 256), ("128v64", 100), ("64", 127),
+                                    ("64", 256)])
 def test_fuzz_generic_formats(fmt, n):
     rng = np.random.default_rng(7 + n)
     nb = 2000
@@ -104,7 +105,7 @@ def test_fuzz_generic_formats(fmt, n):
     assert np.array_equal(got[:, :n], want[:, :n])
 
 
-@pytest.mark.parametrize("fmt,n", [("256v32", 256), ("32", 127), ("256v64", 256)])
+@pytest.mark.parametrize("fmt,n", [("256v32", 256), ("32", 127), ("256v64", 256), ("64", 256)])
 def test_random_bytes_do_not_fault(fmt, n):
     rng = np.random.default_rng(99)
     nb = 4000

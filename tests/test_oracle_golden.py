@@ -5,9 +5,10 @@ import pytest
 
 import golden_io
 import oracle_lib
+import p4_modes
 
 FAMILIES = [("g256v32.bin", "256v32"), ("g128v32.bin", "128v32"), ("g32.bin", "32"),
-            ("g256v64.bin", "256v64"), ("g128v64.bin", "128v64")]
+            ("g256v64.bin", "256v64"), ("g128v64.bin", "128v64"), ("g64.bin", "64")]
 
 
 @pytest.mark.parametrize("fname,fmt", FAMILIES)
@@ -62,3 +63,25 @@ def test_golden_covers_every_mode():
             modes.add("zero" if h == 0 else "plain")
     for m in ["const", "vb_raw", "vb_comp", "bitmap", "bitmap0", "bitmap_xn32", "zero", "plain"]:
         assert m in modes, m
+
+
+def test_golden64_covers_every_mode():
+    """The horizontal 64-bit fixture (p4Enc64 / p4Dec64) reaches every mode,
+    read from the header bytes: all zero, plain, plain with header 63 (width
+    63 or 64), constant, constant with header 63, bitmap patch, vbyte raw and
+    compressed, and the decode-only 0x80 | b header with bx == 0 -- and the
+    compressed vbyte streams carry every vbEnc64 length, 1..9 bytes."""
+    recs = golden_io.load("g64.bin")
+    modes, lens, by_n = set(), set(), {}
+    for i, r in enumerate(recs):
+        m, ls, end = p4_modes.parse64(r.enc, 0, r.n)
+        assert end == len(r.enc), (i, m, end, len(r.enc))
+        assert (m == "bx0") == r.decode_only, (i, m)
+        modes.add(m)
+        lens.update(ls)
+        by_n.setdefault(r.n, set()).add(m)
+    for m in p4_modes.MODES64:
+        assert m in modes, m
+    assert lens == set(range(1, 10)), sorted(lens)
+    assert set(by_n) == {1, 2, 63, 64, 65, 127, 128, 129, 255, 256}
+    assert any(r.d1 and r.start > (1 << 64) - 2000 for r in recs)  # a delta-1 list that wraps 2^64
