@@ -574,6 +574,83 @@ int tpf_lists_intersect(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *
                         uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
                         void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- values at list positions of a resident index -----------------------------
+ * tpf_lists_gather answers nq positional reads against a lists stream, delta-1
+ * or plain: query k is the positions d_pos[d_pos_ptr[k] .. d_pos_ptr[k+1]) of
+ * list j = d_qlist[k], and d_out gets the value at each of them.  Only the
+ * blocks a position names are decoded, and no decoded block is written to
+ * memory.  It is what consumes d_out_tpos of tpf_lists_intersect: the term
+ * frequencies of the hits are this call on the plain stream stored in parallel
+ * with the doc-id stream; on a delta-1 stream it is "the doc id at rank p".
+ *   - The index: the stream, its offsets (OFFSETS CONTRACT), d_list_ptr and
+ *     d_list_unit as tpf_p4ndec256v32_lists_units reads them.  With d1 != 0 the
+ *     skip table d_unit_last (tpf_lists_unit_last) is required and d_start0 ==
+ *     NULL means 0; with d1 == 0 d_unit_last and d_start0 are ignored.  So the
+ *     same d_list_ptr and d_list_unit serve a doc-id stream and the frequency
+ *     stream of the same list lengths: only d_in, in_bytes, d_off and d1 differ.
+ *   - The request: d_pos_ptr (nq + 1 entries) is non-decreasing and need not
+ *     start at 0; pos_values is the readable length of d_pos and the writable
+ *     length of d_out, and nothing of d_pos outside [d_pos_ptr[0],
+ *     d_pos_ptr[nq]) is read.  Positions are list-relative, 0 <= p < n_j.
+ *     Empty segments are allowed anywhere; the same list may be the target of
+ *     many queries; positions may come in any order and may repeat, and every
+ *     occurrence is answered.  Sorted positions make the work minimal: a unit
+ *     is decoded once per run of consecutive request indices that name it, and
+ *     an adjacent query on the same list and unit shares that run.
+ *     d_out_tpos, d_out_ptr and d_qlist of a tpf_lists_intersect call feed this
+ *     call unchanged, on the same stream, with no host step.
+ *   - Definition, per request index i of query k, with p = d_pos[i]: the source
+ *     unit is su = d_list_unit[j] + p / 256; with d1 it is decoded from
+ *     d_start0[j] when it is the list's first unit, else from d_unit_last[su -
+ *     1], as tpf_p4ndec256v32_lists_units decodes it.  d_out[i] is the value at
+ *     index p % 256 of that unit: bit for bit what tpf_p4ndec256v32_lists
+ *     writes at ptr[j] + p (with d1, given a correct table).  A wrong table
+ *     gives wrong values and never an out-of-range access: the table holds
+ *     values, never indices.
+ *   - Output: d_out is parallel to d_pos -- the same index, so there is no
+ *     compaction and no output pointer array.  Nothing is written outside
+ *     [d_pos_ptr[0], d_pos_ptr[nq]).  d_out is only 4-byte aligned and must not
+ *     overlap d_pos.
+ *   - Cost: no kernel is sized by nlists or nunits.  Grids and the workspace
+ *     (four words per position) are sized on the host from pos_values alone.
+ *     Stream bytes are read only at units a position names; beyond them only
+ *     d_list_ptr, d_list_unit and, with d1, d_start0 of targeted lists and
+ *     d_unit_last of the unit before a named one.  Seven launches for up to
+ *     262,144 positions and eight beyond (the run scan then takes a second
+ *     launch): decided on the host by pos_values, whatever the request.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed:
+ *       < nunits          the lowest SOURCE unit, among the units decoded,
+ *                         whose parse disagrees with its offsets; values read
+ *                         from such a unit are unspecified but in bounds;
+ *       nunits + k        the first query k refused by any check
+ *                         tpf_lists_intersect makes on a query: d_qlist[k] >=
+ *                         nlists, list_ptr[j+1] < list_ptr[j], list_unit[j+1] <
+ *                         list_unit[j], list_unit[j+1] > nunits, a unit count
+ *                         different from that of n_j, pos_ptr[k+1] < pos_ptr[k]
+ *                         or pos_ptr[k+1] > pos_values;
+ *       nunits + nq + i   the lowest request index i, inside a segment of a
+ *                         query that is not refused, with d_pos[i] >= n_j.
+ *     On either refusal nothing is written to d_out; when both occur the query
+ *     refusal (the lower code) is the one reported.
+ *   - TPF_EINVAL (decided before any device call): with nq non-zero a null
+ *     d_in, d_off, d_list_ptr, d_list_unit, d_pos_ptr, d_qlist or d_ws, or a
+ *     null d_unit_last when d1 != 0; a null d_pos or d_out while pos_values is
+ *     non-zero; ws_bytes below tpf_lists_gather_workspace_size(nq, pos_values);
+ *     nlists, nunits, nq or pos_values above 0x7FFFFFFF.  nq == 0 is a
+ *     successful no-op that sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_lists_gather_workspace_size(uint64_t nq, uint64_t pos_values);
+int tpf_lists_gather(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                     const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists, int d1,
+                     const uint32_t *d_start0, const uint32_t *d_unit_last,
+                     const uint32_t *d_pos, uint64_t pos_values, const uint64_t *d_pos_ptr /* nq + 1 */,
+                     const uint32_t *d_qlist, uint64_t nq,
+                     uint32_t *d_out /* pos_values entries, parallel to d_pos */,
+                     void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

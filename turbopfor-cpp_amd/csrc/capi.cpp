@@ -684,6 +684,36 @@ int tpf_lists_intersect(const uint8_t * d_in, uint64_t in_bytes, const uint64_t 
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_intersect");
 }
 
+size_t tpf_lists_gather_workspace_size(uint64_t nq, uint64_t pos_values)
+{
+    return tpf::lists_gather_workspace(nq, pos_values);
+}
+
+int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                     const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last,
+                     const uint32_t * d_pos, uint64_t pos_values, const uint64_t * d_pos_ptr, const uint32_t * d_qlist, uint64_t nq,
+                     uint32_t * d_out, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || pos_values > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_gather: nlists, nunits, nq and pos_values are limited to 0x7FFFFFFF");
+    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_pos_ptr || !d_qlist || !d_ws))
+        return fail(TPF_EINVAL, "tpf_lists_gather: null pointer");
+    if (nq && d1 && !d_unit_last)
+        return fail(TPF_EINVAL, "tpf_lists_gather: null d_unit_last (delta-1 needs the skip table of tpf_lists_unit_last)");
+    if (pos_values && (!d_pos || !d_out))
+        return fail(TPF_EINVAL, "tpf_lists_gather: null d_pos or d_out with a non-zero pos_values");
+    if (nq && ws_bytes < tpf_lists_gather_workspace_size(nq, pos_values))
+        return fail(TPF_EINVAL, "tpf_lists_gather: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // d_err is reset by the launcher, together with its workspace header
+    hipError_t e = tpf::launch_lists_gather(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
+                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_pos, pos_values, d_pos_ptr, d_qlist,
+                                            nq, d_out, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_gather");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

@@ -109,6 +109,21 @@ hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const u
                                   const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
                                   uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
                                   uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+// the run scan (p4_scan.h) over a request's 64-index runs: one launch while the
+// run totals fit one tile, launch_run_scan_u32's two beyond (p4_lists_intersect.hip)
+hipError_t ix_scan(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total, hipStream_t s);
+// values at given list positions of a resident index (p4_lists_gather.hip;
+// DESIGN.md 4.12): the intersection's positional twin, for delta-1 and plain
+// streams.  Passes: plan (one thread per query: the checks; one per request
+// index: its query, the position against n_j, its unit) -> item heads and their
+// run scan -> items -> full blocks -> tails (each item's unit decoded into LDS,
+// out[i] = vals[pos[i] % 256]; the tails kernel also writes the verdict of a
+// refusal).  Sized by pos_values alone.
+size_t lists_gather_workspace(uint64_t nq, uint64_t pos_values);
+hipError_t launch_lists_gather(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0,
+                               const uint32_t * unit_last, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
+                               const uint32_t * qlist, uint64_t nq, uint32_t * out, void * ws, unsigned long long * err, hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

@@ -572,6 +572,7 @@ uint32_t flat_grid(uint64_t items, hipStream_t s)
 {
     return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
 }
+} // namespace
 
 // the run scan over the probe's 64-value runs: one launch while they fit one tile, p4_scan.hip's two beyond
 hipError_t ix_scan(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total, hipStream_t s)
@@ -581,7 +582,6 @@ hipError_t ix_scan(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_
     hipLaunchKernelGGL(dev::k_ix_scan1, dim3(1), dim3(256), 0, s, tot, static_cast<uint32_t>(nruns), pre, tile, total);
     return hipGetLastError();
 }
-} // namespace
 
 // nq sizes no array: the queries are read where they lie
 size_t lists_intersect_workspace(uint64_t /*nq*/, uint64_t probe_values) { return IxWs(nullptr, probe_values).bytes; }

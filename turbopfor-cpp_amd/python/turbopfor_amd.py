@@ -167,6 +167,13 @@ def lib():
             L.tpf_lists_intersect.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
                                               c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_lists_intersect.restype = ctypes.c_int
+        # values at list positions of a resident index: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_lists_gather"):
+            L.tpf_lists_gather_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_lists_gather_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_gather.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp,
+                                           c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_gather.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -785,3 +792,40 @@ def lists_intersect(packed, offsets, list_ptr, list_unit, unit_last, probe, prob
                                  _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
                                  out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
+
+
+# ---- values at list positions of a resident index (include/turbopfor_gpu.h tpf_lists_gather) ----
+def lists_gather(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, d1=False, start0=None, unit_last=None, out=None, err=None,
+                 ws=None):
+    """The values at given positions of resident lists: query k is the
+    list-relative positions pos[pos_ptr[k]:pos_ptr[k+1]] (int32 CUDA tensor
+    read as uint32, in any order, repeats allowed, sorted for the least work;
+    pos_ptr: int64 CUDA tensor [nq + 1], non-decreasing) of list qlist[k]
+    (int32 CUDA tensor [nq]), and out[i] is the value at pos[i].  packed /
+    offsets / list_ptr / list_unit / start0: as decn256v32_lists_units;
+    unit_last: the skip table of lists_unit_last, required with d1 and ignored
+    without, so the directory of a doc-id stream also serves the plain
+    frequency stream stored in parallel.  (tpos, out_ptr, qlist) of
+    lists_intersect are (pos, pos_ptr, qlist) here, unchanged.  Only the
+    blocks a position names are decoded, and none is written to memory.  out:
+    int32 CUDA tensor parallel to pos (default: torch.empty_like(pos));
+    entries outside [pos_ptr[0], pos_ptr[nq]) are left alone.  err: optional
+    int64 CUDA tensor [1] (-1 = clean).  Asynchronous: no device-to-host
+    read.  Returns out."""
+    import torch
+
+    if d1 and unit_last is None:
+        raise ValueError("lists_gather: d1=True needs unit_last (lists_unit_last)")
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nq = qlist.numel()
+    if out is None:
+        out = torch.empty_like(pos)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_gather_workspace_size(nq, pos.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_lists_gather(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
+                              _ptr(start0), _ptr(unit_last), _ptr(pos), pos.numel(), _ptr(pos_ptr), _ptr(qlist), nq, _ptr(out), _ptr(ws),
+                              ws.numel(), _ptr(err), _stream(torch)))
+    return out
