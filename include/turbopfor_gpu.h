@@ -651,6 +651,103 @@ int tpf_lists_gather(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_o
                      uint32_t *d_out /* pos_values entries, parallel to d_pos */,
                      void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- postings appended to a resident index ------------------------------------
+ * tpf_lists_append extends the lists of a lists stream: list j of the result is
+ * L_j ++ A_j, L_j being list j of the old index (empty for j >= nlists, which is
+ * how new lists arrive) and A_j = d_add[d_add_ptr[j] .. d_add_ptr[j+1]).  A
+ * 256v32 block's bytes depend on its 256 values and the value before it only,
+ * so every full block of the old stream is moved as bytes; only the p4Enc32
+ * tail of a list that receives values is decoded, joined with them and encoded
+ * again.  Every table the readers need comes out of the same call: the result
+ * feeds tpf_lists_intersect, tpf_lists_gather and tpf_p4ndec256v32_lists_units
+ * with no further pass.  Appending to an empty index is encoding with the tables.
+ *   - The old index: the stream, its offsets (OFFSETS CONTRACT), d_list_ptr and
+ *     d_list_unit as tpf_p4ndec256v32_lists_units reads them; with d1 != 0 the
+ *     skip table d_unit_last (tpf_lists_unit_last) is required.  d_start0 has
+ *     nlists_out entries (NULL = 0; ignored with d1 == 0).  nlists == 0 or nunits
+ *     == 0 is an empty old index: d_in, d_off, d_list_ptr and d_list_unit are
+ *     then not read and may be NULL.
+ *   - The additions: nlists_out >= nlists; d_add_ptr (nlists_out + 1 entries) is
+ *     non-decreasing and need not start at 0; add_values is the readable length
+ *     of d_add, and nothing of d_add outside [d_add_ptr[0], d_add_ptr[nlists_out])
+ *     is read.  Empty additions and empty lists are allowed anywhere.
+ *   - The result: d_list_ptr_out[0] = 0 and d_list_ptr_out[j+1] -
+ *     d_list_ptr_out[j] = |L_j| + |A_j|; d_list_unit_out is what
+ *     tpf_lists_unit_base gives for it, its last entry the result's unit count
+ *     nunits_out.  For an old stream written by this library's encoders d_out and
+ *     d_off_out[0 .. nunits_out] are byte for byte and offset for offset what
+ *     tpf_p4nenc256v32_lists writes for the lists L_j ++ A_j with the same d1 and
+ *     d_start0 (with d1: given a correct d_unit_last); for any old stream that
+ *     passes the checks below the result decodes to L_j ++ A_j.  With d1,
+ *     d_unit_last_out[0 .. nunits_out) is what tpf_lists_unit_last gives for the
+ *     new stream.  The outputs must not overlap the inputs: the call is out of
+ *     place and the caller swaps buffers.
+ *   - What is read of the old stream, with r_j = |L_j| % 256: the |L_j| / 256
+ *     full blocks of every list are copied and never parsed; the tail is parsed
+ *     only when r_j > 0 and |A_j| > 0, and copied otherwise.  Interior offsets of
+ *     copied units are carried over shifted and not checked; the ends of each
+ *     copied byte range are.  With d1 the first re-encoded block of list j
+ *     starts from d_start0[j] when |L_j| < 256, else from d_unit_last of the
+ *     list's last full unit.  The table holds values, never indices: a wrong
+ *     table gives wrong bytes and never an out-of-range access.
+ *   - Capacities: units_cap is the capacity of d_off_out (units_cap + 1 entries)
+ *     and of d_unit_last_out.  tpf_lists_append_units_bound = nunits + add_values
+ *     / 256 + min(nlists_out, add_values) always suffices (ceil((a + m) / 256) <=
+ *     ceil(a / 256) + m / 256 + 1 for m > 0), and so does tpf_lists_append_bound
+ *     = in_bytes + tpf_p4nenc256v32_lists_bound(add_values + 255 T, T), T =
+ *     min(nlists_out, add_values), for out_cap.  Both are advice, not
+ *     preconditions: nothing is written at or past a capacity.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed; the lowest code is the one reported:
+ *       < nunits                  the lowest old tail unit, among those parsed,
+ *                                 whose parse disagrees with its offsets; what is
+ *                                 written is unspecified but in bounds;
+ *       nunits + j                the first list j < nlists_out that fails a
+ *                                 structure check: list_ptr[j+1] < list_ptr[j]; a
+ *                                 d_list_unit span different from the unit count
+ *                                 of |L_j|; list_unit[j+1] > nunits; a copied byte
+ *                                 range with off[lo] > off[hi] or off[hi] >
+ *                                 in_bytes; add_ptr[j+1] < add_ptr[j]; add_ptr[j+1]
+ *                                 > add_values.  Nothing is written, in any output;
+ *       nunits + nlists_out       nunits_out > units_cap, or above 0x7FFFFFFF: only
+ *                                 d_list_ptr_out and d_list_unit_out are written,
+ *                                 completely, so the caller reads what to allocate;
+ *       nunits + nlists_out + 1   the stream is longer than out_cap: everything
+ *                                 is written except d_out, so
+ *                                 d_off_out[nunits_out] is what to allocate.
+ *   - TPF_EINVAL (decided before any device call): nlists_out < nlists; with
+ *     nlists_out non-zero a null d_add_ptr, d_out (with out_cap non-zero),
+ *     d_off_out, d_list_ptr_out, d_list_unit_out or d_ws, a null d_in, d_off,
+ *     d_list_ptr or d_list_unit with nlists and nunits non-zero, a null
+ *     d_unit_last or d_unit_last_out when d1 != 0, a null d_add while add_values
+ *     is non-zero; ws_bytes below tpf_lists_append_workspace_size(nunits,
+ *     nlists_out, add_values); nunits, nlists_out, units_cap or add_values above
+ *     0x7FFFFFFF.  nlists_out == 0 is a successful no-op that writes
+ *     d_list_ptr_out[0] = 0, d_list_unit_out[0] = 0, d_off_out[0] = 0 and a
+ *     clean d_err.
+ *   - Cost: the stitch pass moves the whole index once, partitioned by output
+ *     bytes (16,384 per wave), not by list; everything else is sized by
+ *     nlists_out, add_values and units_cap.  The workspace holds the staged
+ *     values (add_values + 255 min(T, nunits)), their encoded bytes and the
+ *     encoder's workspace.  Everything is enqueued on `stream`: no host
+ *     synchronisation and no device-to-host copy; at most 23 launches, their
+ *     number and their grids fixed by the arguments' sizes, not their contents.
+ * d_ws: device workspace, at least 8-byte aligned. */
+uint64_t tpf_lists_append_units_bound(uint64_t nunits, uint64_t nlists_out, uint64_t add_values);
+uint64_t tpf_lists_append_bound(uint64_t in_bytes, uint64_t nlists_out, uint64_t add_values);
+size_t   tpf_lists_append_workspace_size(uint64_t nunits, uint64_t nlists_out, uint64_t add_values);
+int tpf_lists_append(
+    /* the old index */   const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                          const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                          int d1, const uint32_t *d_start0 /* nlists_out entries, or NULL = 0 */,
+                          const uint32_t *d_unit_last /* required when d1 != 0 */,
+    /* the additions */   const uint32_t *d_add, uint64_t add_values, const uint64_t *d_add_ptr /* nlists_out + 1 */,
+                          uint64_t nlists_out,
+    /* the new index */   uint8_t *d_out, uint64_t out_cap, uint64_t *d_off_out /* units_cap + 1 */, uint64_t units_cap,
+                          uint64_t *d_list_ptr_out /* nlists_out + 1 */, uint32_t *d_list_unit_out /* nlists_out + 1 */,
+                          uint32_t *d_unit_last_out /* units_cap; required when d1 != 0, ignored otherwise */,
+                          void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

@@ -714,6 +714,58 @@ int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_gather");
 }
 
+// ---- postings appended to a resident index (p4_lists_append.hip)
+uint64_t tpf_lists_append_units_bound(uint64_t nunits, uint64_t nlists_out, uint64_t add_values)
+{
+    return nunits + add_values / 256u + std::min(nlists_out, add_values);
+}
+
+uint64_t tpf_lists_append_bound(uint64_t in_bytes, uint64_t nlists_out, uint64_t add_values)
+{
+    const uint64_t T = std::min(nlists_out, add_values);
+    return in_bytes + tpf_p4nenc256v32_lists_bound(add_values + 255u * T, T);
+}
+
+size_t tpf_lists_append_workspace_size(uint64_t nunits, uint64_t nlists_out, uint64_t add_values)
+{
+    return tpf::lists_append_workspace(nunits, nlists_out, add_values);
+}
+
+int tpf_lists_append(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                     const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last,
+                     const uint32_t * d_add, uint64_t add_values, const uint64_t * d_add_ptr, uint64_t nlists_out, uint8_t * d_out,
+                     uint64_t out_cap, uint64_t * d_off_out, uint64_t units_cap, uint64_t * d_list_ptr_out, uint32_t * d_list_unit_out,
+                     uint32_t * d_unit_last_out, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (nlists_out < nlists)
+        return fail(TPF_EINVAL, "tpf_lists_append: nlists_out is below nlists (lists are never removed)");
+    if (nunits > 0x7FFFFFFFull || nlists_out > 0x7FFFFFFFull || units_cap > 0x7FFFFFFFull || add_values > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_append: nunits, nlists_out, units_cap and add_values are limited to 0x7FFFFFFF");
+    if (!d_off_out || !d_list_ptr_out || !d_list_unit_out)
+        return fail(TPF_EINVAL, "tpf_lists_append: null pointer");
+    if (nlists_out && (!d_add_ptr || !d_ws || (out_cap && !d_out)))
+        return fail(TPF_EINVAL, "tpf_lists_append: null pointer");
+    if (nlists && nunits && (!d_in || !d_off || !d_list_ptr || !d_list_unit))
+        return fail(TPF_EINVAL, "tpf_lists_append: null pointer (the old index)");
+    if (nlists_out && d1 && (!d_unit_last_out || (nlists && nunits && !d_unit_last)))
+        return fail(TPF_EINVAL,
+                    "tpf_lists_append: null d_unit_last or d_unit_last_out (delta-1 needs the skip table of tpf_lists_unit_last)");
+    if (add_values && !d_add)
+        return fail(TPF_EINVAL, "tpf_lists_append: null d_add with a non-zero add_values");
+    if (nlists_out && ws_bytes < tpf_lists_append_workspace_size(nunits, nlists_out, add_values))
+        return fail(TPF_EINVAL, "tpf_lists_append: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_append(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
+                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_add, add_values, d_add_ptr,
+                                            nlists_out, d_out, out_cap, d_off_out, units_cap, d_list_ptr_out, d_list_unit_out,
+                                            d1 ? d_unit_last_out : nullptr, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_append");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

@@ -24,6 +24,9 @@ namespace tpf::dev
 constexpr uint32_t kRecTail = 0x80000000u;
 constexpr uint32_t kRecList = 0x7FFFFFFFu;
 
+// bytes of d_out one wave of the append's stitch pass moves (p4_lists_append.hip)
+constexpr uint32_t kListsAppendTile = 16384;
+
 struct ListsHdr
 {
     unsigned long long bad;   // first list j with ptr[j+1] < ptr[j] or ptr[j+1] > out_values (~0: none)
@@ -58,6 +61,18 @@ size_t lists_enc_workspace(uint64_t nunits, uint64_t nlists);
 hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint64_t * ptr, uint64_t nlists, bool d1,
                             const uint32_t * start0, uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t nunits, void * ws,
                             unsigned long long * err, hipStream_t s);
+// the same passes over lists planned on the device (p4_lists_enc.hip): the
+// caller fills the view -- header, ubase (nlists + 1), unit records -- and
+// units_cap bounds the unit count, which the header holds
+struct ListsEncPlanView
+{
+    dev::ListsHdr * hdr;
+    uint32_t * ubase;
+    uint32_t * rec;
+};
+ListsEncPlanView lists_enc_plan_view(void * ws, uint64_t units_cap, uint64_t nlists);
+hipError_t launch_lists_enc_planned(const uint32_t * in, const uint64_t * ptr, uint64_t nlists, bool d1, const uint32_t * start0,
+                                    uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t units_cap, void * ws, hipStream_t s);
 hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                             uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
                             unsigned long long * err, hipStream_t s);
@@ -124,6 +139,20 @@ hipError_t launch_lists_gather(const uint8_t * in, uint64_t in_bytes, const uint
                                const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0,
                                const uint32_t * unit_last, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
                                const uint32_t * qlist, uint64_t nq, uint32_t * out, void * ws, unsigned long long * err, hipStream_t s);
+// postings appended to the lists of a resident index (p4_lists_append.hip;
+// DESIGN.md 4.13).  Passes: plan (one thread per output list: the checks, what
+// of its old tail is staged, its new units) -> four run scans -> heads (the
+// verdict, both directories, the staged lists) -> stage (the additions, the old
+// tails decoded in front of them) -> the encoder's passes over the staged lists
+// -> segs (every list's first output byte, the capacity) -> offsets (d_off_out,
+// d_unit_last_out) -> stitch (a wave per kListsAppendTile bytes of d_out).
+// Sized by nunits, nlists_out and add_values alone.
+size_t lists_append_workspace(uint64_t nunits, uint64_t nlists_out, uint64_t add_values);
+hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
+                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
+                               const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t nlists_out, uint8_t * out,
+                               uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out,
+                               uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

@@ -1,0 +1,751 @@
+// p4_lists_append.hip -- tpf_lists_append: postings appended to the lists of a
+// resident index in one submission with no host round trip
+// (include/turbopfor_gpu.h).  A 256v32 block's bytes depend on
+// its 256 values and the value before it only, so every full block of the old
+// stream is moved as bytes; only the p4Enc32 tail of a list that receives
+// values is decoded, put in front of the list's additions and encoded again.
+//   plan   : a thread per output list: the checks, the values of its old tail
+//            that are staged (tv), its new units (m), the bytes of the tail
+//            it drops (db); four run totals per 64 lists
+//   scans  : run scans of the four (p4_scan.h)
+//   heads  : the verdict, then per list d_list_ptr_out, d_list_unit_out, the
+//            staged lists' pointers / unit bases / unit records / delta-1
+//            starts, and the prefix of the kept bytes
+//   stage  : the additions (a thread per value) and the old tails (k_un_tails's
+//            pipeline, a wave per 16 lists) into one dense value array
+//   encode : the many-lists encoder's passes (p4_lists_enc.hip) over the staged
+//            lists into a byte buffer of the workspace, with their offsets
+//   segs   : a thread per list: where its bytes start in d_out; the capacity
+//   offsets: a thread per output unit: d_off_out and d_unit_last_out
+//   stitch : the output stream cut into kListsAppendTile-byte tiles of d_out, a wave
+//            per tile: it finds its lists by a search over the lists' starts
+//            and moves each list's kept bytes (from d_in) and new bytes (from
+//            the workspace) with destination-aligned 16-byte stores
+// Every kernel after the heads reads the go flag of the header first.
+#include "p4_lists.h"
+
+#include "p4_dec256v32.h"
+#include "p4_generic.h"
+#include "p4_lists_dev.h"
+#include "p4_scan.h"
+#include "tpf_kernels.h"
+#include "turbopfor_gpu.h"
+
+#include <algorithm>
+
+namespace tpf::dev
+{
+
+constexpr uint32_t kAppLaneBytes = 128; // the stitch pass: a list with no more bytes in the tile is moved by one lane
+constexpr uint32_t kAppTailMax = 4096; // more bytes than a p4Enc32 unit of <= 255 values can have
+
+struct AppHdr
+{
+    unsigned long long bad;  // first list that fails a structure check (~0: none)
+    unsigned long long tbad; // lowest parsed tail unit whose offsets lie outside the stream (~0: none)
+    unsigned long long tv, tt, m, db; // totals of the four scans
+    unsigned long long nunits_out;
+    uint32_t go;  // the heads pass: structure, tails' offsets and units_cap are sound
+    uint32_t fit; // the segs pass: the stream fits out_cap
+};
+
+struct AppArgs
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    uint64_t nunits;
+    const uint64_t * lptr;
+    const uint32_t * lunit;
+    uint64_t nlists;
+    const uint32_t * start0;
+    const uint32_t * unit_last;
+    const uint32_t * add;
+    uint64_t add_values;
+    const uint64_t * aptr;
+    uint64_t n; // nlists_out
+    uint8_t * out;
+    uint64_t out_cap;
+    uint64_t * off_out;
+    uint64_t units_cap;
+    uint64_t * lptr_out;
+    uint32_t * lunit_out;
+    uint32_t * ulast_out;
+    unsigned long long * err;
+    // workspace
+    AppHdr * hdr;
+    uint32_t *tv_tot, *tt_tot, *m_tot, *db_tot; // run totals
+    const uint64_t *tv_pre, *tv_tile, *tt_pre, *tt_tile, *m_pre, *m_tile, *db_pre, *db_tile;
+    uint32_t *tv, *m, *db;    // per list
+    uint32_t * sst;           // per list: delta-1 start of its staged values
+    uint64_t * sptr;          // n + 1: staged lists
+    uint64_t * kbpre;         // n + 1: kept bytes of the lists before
+    uint64_t * lstart;        // n + 1: first output byte of every list
+    uint32_t * stage;         // staged values
+    uint64_t * noff;          // offsets of the staged lists' units in sbytes
+    uint8_t * sbytes;         // their bytes
+    ListsHdr * ehdr;          // the encoder's view (p4_lists.h)
+    uint32_t * subase;        // n + 1: first staged unit of every list
+    uint32_t * rec;           // records of the staged units
+    uint64_t su_cap;
+    uint64_t ebase; // the caller's nunits: the base of the list codes of d_err
+};
+
+__device__ __forceinline__ void app_err(unsigned long long * err, unsigned long long v)
+{
+    if (err != nullptr)
+        atomicMin(err, v);
+}
+
+__global__ void k_app_reset(AppHdr * hdr, ListsHdr * ehdr)
+{
+    if (threadIdx.x == 0)
+    {
+        *hdr = AppHdr{~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0u, 0u};
+        if (ehdr != nullptr)
+            *ehdr = ListsHdr{0ull, 0ull}; // no go until the heads pass says so
+    }
+}
+
+// nlists_out == 0: the empty result
+__global__ void k_app_empty(uint64_t * lptr_out, uint32_t * lunit_out, uint64_t * off_out)
+{
+    if (threadIdx.x == 0)
+    {
+        lptr_out[0] = 0ull;
+        lunit_out[0] = 0u;
+        off_out[0] = 0ull;
+    }
+}
+
+// ---- plan ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_app_plan(const AppArgs A)
+{
+    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint64_t j = gid;
+    uint32_t tv = 0u, m = 0u, db = 0u;
+    if (j < A.n)
+    {
+        const bool old = j < A.nlists;
+        const uint64_t p0 = old ? A.lptr[j] : 0ull, p1 = old ? A.lptr[j + 1u] : 0ull;
+        const uint64_t a0 = A.aptr[j], a1 = A.aptr[j + 1u];
+        const uint64_t oldn = p1 - p0;
+        const uint64_t cnt = (oldn >> 8) + ((oldn & 255u) != 0u ? 1u : 0u);
+        const uint64_t lu0 = old ? A.lunit[j] : 0u, lu1 = old ? A.lunit[j + 1u] : 0u;
+        bool bad = p1 < p0 || a1 < a0 || a1 > A.add_values || lu1 - lu0 != cnt || lu1 > A.nunits;
+        if (!bad)
+        {
+            const uint64_t addn = a1 - a0; // < 2^31
+            const uint32_t r = static_cast<uint32_t>(oldn & 255u);
+            const bool tt = r != 0u && addn != 0u;
+            const uint64_t keep = cnt - (tt ? 1u : 0u);
+            if (cnt != 0u)
+            {
+                // the ends of the copied range; the dropped tail's offsets
+                const uint64_t o0 = A.off[lu0], o1 = A.off[lu0 + keep];
+                bad = o0 > o1 || o1 > A.in_bytes;
+                if (!bad && tt)
+                {
+                    const uint64_t o2 = A.off[lu1];
+                    if (o2 < o1 || o2 > A.in_bytes || o2 - o1 > kAppTailMax)
+                        atomicMin(&A.hdr->tbad, static_cast<unsigned long long>(lu1 - 1u));
+                    else
+                        db = static_cast<uint32_t>(o2 - o1);
+                }
+            }
+            if (!bad)
+            {
+                tv = tt ? r : 0u;
+                m = static_cast<uint32_t>((tv + addn + 255u) >> 8);
+            }
+            else
+                db = 0u;
+        }
+        if (bad)
+            atomicMin(&A.hdr->bad, static_cast<unsigned long long>(j));
+        A.tv[j] = tv;
+        A.m[j] = m;
+        A.db[j] = db;
+    }
+    // gid < 64 * runs for every thread of the grid's last block up to the run's end
+    const uint64_t run = gid / 64u;
+    if (run * 64u < A.n)
+    {
+        publish_run_total(A.tv_tot, run, tv, t);
+        publish_run_total(A.tt_tot, run, tv != 0u ? 1u : 0u, t);
+        publish_run_total(A.m_tot, run, m, t);
+        publish_run_total(A.db_tot, run, db, t);
+    }
+    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
+    for (uint64_t u = gid; u < A.su_cap; u += gsz)
+        A.rec[u] = 0u;
+}
+
+// ---- heads --------------------------------------------------------------------
+template <bool D1>
+__global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
+{
+    const uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const AppHdr h = *A.hdr;
+    if (h.bad != ~0ull || h.tbad != ~0ull)
+    {
+        if (j == 0)
+            app_err(A.err, h.tbad != ~0ull ? h.tbad : A.ebase + h.bad);
+        return;
+    }
+    const uint64_t lu00 = A.nlists != 0u ? A.lunit[0] : 0u;
+    const uint64_t luN = A.nlists != 0u ? A.lunit[A.nlists] : 0u;
+    const uint64_t nuo = (luN - lu00) - h.tt + h.m;
+    const bool ufit = nuo <= A.units_cap && nuo <= 0x7FFFFFFFull;
+    const bool in = j < A.n;
+    const uint32_t tv = in ? A.tv[j] : 0u, m = in ? A.m[j] : 0u, db = in ? A.db[j] : 0u;
+    const uint32_t ttv = tv != 0u ? 1u : 0u;
+    // exclusive prefixes: the run's base plus the wave's scan (every lane of the wave takes part)
+    uint64_t TV = wave_incl_scan(tv) - tv, TT = wave_incl_scan(ttv) - ttv, M = wave_incl_scan(m) - m, DB = wave_incl_scan(db) - db;
+    if (j > A.n)
+        return;
+    if (in)
+    {
+        const uint64_t run = j / 64u;
+        TV += run_base(A.tv_pre, A.tv_tile, run);
+        TT += run_base(A.tt_pre, A.tt_tile, run);
+        M += run_base(A.m_pre, A.m_tile, run);
+        DB += run_base(A.db_pre, A.db_tile, run);
+    }
+    else
+    {
+        TV = h.tv, TT = h.tt, M = h.m, DB = h.db;
+    }
+    const uint64_t jo = j < A.nlists ? j : A.nlists; // lists past the old index are empty there
+    const uint64_t lu = A.nlists != 0u ? A.lunit[jo] : 0u;
+    const uint64_t oldoff = A.nlists != 0u ? A.lptr[jo] - A.lptr[0] : 0ull;
+    const uint64_t a0 = A.aptr[j];
+    const uint64_t addoff = a0 - A.aptr[0];
+    A.lptr_out[j] = oldoff + addoff;
+    A.lunit_out[j] = static_cast<uint32_t>((lu - lu00) - TT + M);
+    if (!ufit)
+    {
+        if (j == A.n)
+            app_err(A.err, A.ebase + A.n);
+        return;
+    }
+    A.sptr[j] = addoff + TV;
+    A.subase[j] = static_cast<uint32_t>(M);
+    A.kbpre[j] = (A.nunits != 0u && A.nlists != 0u ? A.off[lu] - A.off[lu00] : 0ull) - DB;
+    if (in)
+    {
+        const uint64_t addn = A.aptr[j + 1u] - a0;
+        const bool tail = ((tv + addn) & 255u) != 0u;
+        if (m == 1u)
+            A.rec[M] = static_cast<uint32_t>(j + 1u) | (tail ? kRecTail : 0u);
+        else if (m != 0u)
+        {
+            A.rec[M] = static_cast<uint32_t>(j + 1u);
+            if (tail)
+                A.rec[M + m - 1u] = kRecTail;
+        }
+        if constexpr (D1)
+        {
+            // the staged values continue the list: from the last kept full block, or from start0
+            const uint64_t oldn = j < A.nlists ? A.lptr[j + 1u] - A.lptr[j] : 0ull;
+            A.sst[j] = oldn < 256u ? (A.start0 != nullptr ? A.start0[j] : 0u) : A.unit_last[lu + (oldn >> 8) - 1u];
+        }
+    }
+    else
+    {
+        *A.ehdr = ListsHdr{~0ull, h.m};
+        if (h.m == 0u)
+            A.noff[0] = 0ull;
+        A.hdr->nunits_out = nuo;
+        A.hdr->go = 1u;
+    }
+}
+
+// ---- stage: the additions -----------------------------------------------------
+// The last j in [0, n) with tab[j] <= x, for tab[0] <= x < tab[n]: find_list's
+// cooperative search (p4_lists_dev.h) over 64-bit entries.
+template <class E>
+__device__ __forceinline__ uint32_t find_start(const E * __restrict tab, uint32_t n, uint64_t x, uint32_t t)
+{
+    uint32_t lo = 0u, hi = n;
+    while (hi - lo > 1u)
+    {
+        const uint32_t step = (hi - lo + 63u) / 64u;
+        const uint64_t p = static_cast<uint64_t>(lo) + static_cast<uint64_t>(t + 1u) * step;
+        const bool le = p < hi && tab[p] <= x;
+        const uint32_t c = static_cast<uint32_t>(__builtin_popcountll(__ballot(le)));
+        lo = uni(lo + c * step);
+        hi = uni(umin32(hi, lo + step));
+    }
+    return lo;
+}
+
+// The same for one lane, from a j0 known to be at or before the answer (the wave's first item's): a galloping search, one
+// probe when the item lies in list j0 as most do.
+template <class E>
+__device__ __forceinline__ uint32_t gallop(const E * __restrict tab, uint32_t n, uint32_t j0, uint64_t x)
+{
+    uint32_t lo = j0, step = 1u;
+    while (lo + step < n && tab[lo + step] <= x)
+    {
+        lo += step;
+        step *= 2u;
+    }
+    uint32_t hi = umin32(lo + step, n); // tab[hi] > x (tab[n] > x)
+    while (hi - lo > 1u)
+    {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (tab[mid] <= x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_app_stage_add(const AppArgs A)
+{
+    if (A.hdr->go == 0u)
+        return;
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint64_t p = A.aptr[0] + i, end = A.aptr[A.n];
+    const uint64_t pw = p - t; // the wave's first value
+    if (pw >= end)
+        return;
+    // the last j with aptr[j] <= p (aptr[0] <= p < aptr[n]): the wave's first value by the cooperative search, the others from it
+    const uint32_t j0 = find_start(A.aptr, static_cast<uint32_t>(A.n), pw, t);
+    if (i >= A.add_values || p >= end)
+        return;
+    const uint32_t lo = gallop(A.aptr, static_cast<uint32_t>(A.n), j0, p);
+    A.stage[A.sptr[lo] + A.tv[lo] + (p - A.aptr[lo])] = A.add[p];
+}
+
+// ---- stage: the old tails -----------------------------------------------------
+// k_un_tails's shape (p4_lists_units.hip): every wave owns kRunDefault
+// consecutive lists with the generic decoder's pipeline; lane t holds list
+// first + t's old tail -- the list's last unit, tv values -- or nothing.
+template <bool D1, uint32_t NC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_app_stage_tails(const AppArgs A)
+{
+    __shared__ uint32_t slots[4][kListSlot / 4];
+    __shared__ uint32_t scratch[4][kListScratchU32];
+    if (A.hdr->go == 0u)
+        return;
+    constexpr uint32_t kRun = kRunDefault;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    uint32_t * slot = slots[wv];
+    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
+    const uint64_t in_end = in_base + A.in_bytes;
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    if (first >= A.nlists)
+        return;
+    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nlists - first));
+    const uint64_t k = first + t;
+    const uint32_t cnt = t < n ? A.tv[k] : 0u;
+    const bool has = cnt != 0u;
+    const uint64_t hasmask = __ballot(has);
+    if (hasmask == 0ull)
+        return;
+    const uint32_t su = has ? A.lunit[k + 1u] - 1u : 0u; // the list's last unit
+    const uint64_t o = has ? A.off[su] : 0ull;
+    const uint64_t e = has ? A.off[su + 1u] : 0ull;
+    RunPlaneT<kListSlot> P;
+    P.init(in_base, in_end, o, e, has);
+    const uint64_t opos = has ? A.sptr[k] : 0ull;
+    uint32_t startv = 0u;
+    if constexpr (D1)
+    {
+        if (has)
+            startv = A.sst[k];
+    }
+    uint64_t badmask = 0u;
+    auto consume = [&](const Chunk & c, uint32_t jj) {
+        if (((hasmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t ctl = P.stage(c, jj, slot, t);
+        const uint32_t cj = rl(cnt, jj);
+        uint32_t x[4], cm;
+        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
+        if constexpr (D1)
+            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        uint32_t * op = A.stage + readlane_u64(opos, jj);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+            if (t + 64u * q < cj)
+                op[t + 64u * q] = x[q];
+        wave_lds_sync();
+        if (used != rl(P.len, jj))
+            badmask |= 1ull << jj;
+    };
+    Chunk C[NC];
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        P.template issue<0>(C[q], q, t);
+    bool more = true;
+    for (uint32_t jb = 0; more; jb += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
+                consume(C[q], jb + q);
+                more = jb + q + 1 < n;
+            }
+        }
+    }
+    if (A.err != nullptr && badmask != 0u)
+    {
+        const uint32_t mn = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
+        if (t == 0)
+            atomicMin(A.err, static_cast<unsigned long long>(mn));
+    }
+}
+
+// ---- segs: where every list's bytes start, and the capacity -----------------------
+__global__ __launch_bounds__(256) void k_app_segs(const AppArgs A)
+{
+    if (A.hdr->go == 0u)
+        return;
+    const uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (j > A.n)
+        return;
+    const uint64_t s = A.kbpre[j] + A.noff[A.subase[j]];
+    A.lstart[j] = s;
+    if (j == A.n)
+    {
+        A.off_out[A.hdr->nunits_out] = s;
+        if (s > A.out_cap)
+            app_err(A.err, A.ebase + A.n + 1u);
+        else
+            A.hdr->fit = 1u;
+    }
+}
+
+// ---- offsets ------------------------------------------------------------------
+template <bool D1>
+__global__ __launch_bounds__(256) void k_app_offsets(const AppArgs A)
+{
+    if (A.hdr->go == 0u)
+        return;
+    const uint64_t u = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint64_t nuo = A.hdr->nunits_out;
+    if (u - t >= nuo)
+        return;
+    // the last j with lunit_out[j] <= u (lunit_out[0] = 0 <= u < lunit_out[n]), as k_app_stage_add finds its list
+    const uint32_t j0 = find_start(A.lunit_out, static_cast<uint32_t>(A.n), u - t, t);
+    if (u >= nuo)
+        return;
+    const uint64_t j = gallop(A.lunit_out, static_cast<uint32_t>(A.n), j0, u);
+    const uint32_t local = static_cast<uint32_t>(u) - A.lunit_out[j];
+    const bool old = j < A.nlists;
+    const uint32_t lu = old ? A.lunit[j] : 0u;
+    const uint32_t keep = old ? A.lunit[j + 1u] - lu - (A.tv[j] != 0u ? 1u : 0u) : 0u;
+    if (local < keep)
+    {
+        A.off_out[u] = A.lstart[j] + (A.off[lu + local] - A.off[lu]);
+        if constexpr (D1)
+            A.ulast_out[u] = A.unit_last[lu + local];
+    }
+    else
+    {
+        const uint32_t v = local - keep; // the list's staged unit
+        A.off_out[u] = A.kbpre[j + 1u] + A.noff[A.subase[j] + v];
+        if constexpr (D1)
+            A.ulast_out[u] = A.stage[min_u64(A.sptr[j] + 256ull * (v + 1u), A.sptr[j + 1u]) - 1u];
+    }
+}
+
+// ---- stitch -------------------------------------------------------------------
+// dst[0 .. n) = src[0 .. n), a wave's work: 16-byte stores at the destination's
+// 16-byte boundaries, each fed by aligned dword loads and v_alignbyte (k_copy16,
+// host_copy.hip): a vector is moved that way only when every dword it reads
+// holds a byte of src[0 .. n), the edges go byte by byte.
+__device__ __forceinline__ void wave_move(uint8_t * dst, const uint8_t * src, uint32_t n, uint32_t t)
+{
+    const uint32_t head = umin32(n, (16u - static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src + head);
+    const uint32_t sh = static_cast<uint32_t>(s0 & 3u);
+    uint32_t nvec = (n - head) / 16u;
+    // a shifted vector reads its last source bytes from a fifth dword, a
+    // matching one reads four: both stay inside the source
+    const uint32_t * w = reinterpret_cast<const uint32_t *>(s0 - sh);
+    u32x4 * d = reinterpret_cast<u32x4 *>(dst + head);
+    if (sh == 0u)
+    {
+        for (uint32_t i = t; i < nvec; i += 64u)
+        {
+            const uint32_t * q = w + 4u * i;
+            const u32x4 v{q[0], q[1], q[2], q[3]};
+            __builtin_nontemporal_store(v, d + i);
+        }
+    }
+    else
+    {
+        for (uint32_t i = t; i < nvec; i += 64u)
+        {
+            const uint32_t * q = w + 4u * i;
+            const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4];
+            const u32x4 v{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                          __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
+            __builtin_nontemporal_store(v, d + i);
+        }
+    }
+    const uint32_t tail0 = head + 16u * nvec; // n - tail0 < 16
+    if (t < head)
+        dst[t] = src[t];
+    else if (t - head < n - tail0)
+        dst[tail0 + (t - head)] = src[tail0 + (t - head)];
+}
+
+__global__ __launch_bounds__(256) void k_app_stitch(const AppArgs A)
+{
+    if (A.hdr->go == 0u || A.hdr->fit == 0u)
+        return;
+    const uint32_t t = threadIdx.x & 63u;
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    const uint32_t n = static_cast<uint32_t>(A.n);
+    const uint64_t total = A.lstart[n];
+    const uint64_t x0 = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kListsAppendTile;
+    if (x0 >= total)
+        return;
+    const uint64_t x1 = min_u64(x0 + kListsAppendTile, total);
+    uint32_t jb = find_start(A.lstart, n, x0, t);
+    for (;;)
+    {
+        // lane t: list jb + t, its bytes [s, e) of the output
+        const uint32_t j = jb + t;
+        const bool in = j < n;
+        const uint64_t s = in ? A.lstart[j] : total;
+        const uint64_t e = in ? A.lstart[j + 1u] : total;
+        const bool act = in && s < x1 && e > x0 && e > s;
+        uint64_t kb = 0ull, ksrc = 0ull, nsrc = 0ull;
+        if (act)
+        {
+            kb = A.kbpre[j + 1u] - A.kbpre[j];
+            if (kb != 0ull)
+                ksrc = reinterpret_cast<uint64_t>(A.in) + A.off[A.lunit[j]];
+            nsrc = reinterpret_cast<uint64_t>(A.sbytes) + A.noff[A.subase[j]];
+        }
+        // a list of at most kAppLaneBytes bytes inside the tile is moved by its own lane, 64 lists at a time: a tile of
+        // thousands of one-value lists would otherwise pay one memory round trip per list
+        const uint64_t c0 = s > x0 ? s : x0, c1 = min_u64(e, x1);
+        const bool small = act && c1 - c0 <= kAppLaneBytes;
+        if (small)
+        {
+            const uint64_t lk = s + kb;
+            const uint64_t kp = ksrc - s, np = nsrc - lk; // + b: the source address of byte b of the output, kept / new
+            for (uint64_t b0 = c0; b0 < c1; b0 += 8u)
+            {
+                uint8_t v[8];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q)
+                    v[q] = b0 + q < c1 ? *reinterpret_cast<const uint8_t *>((b0 + q < lk ? kp : np) + b0 + q) : uint8_t(0);
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q)
+                    if (b0 + q < c1)
+                        A.out[b0 + q] = v[q];
+            }
+        }
+        uint64_t mask = __ballot(act && !small);
+        while (mask != 0ull)
+        {
+            const uint32_t l = static_cast<uint32_t>(__builtin_ctzll(mask));
+            mask &= mask - 1ull;
+            const uint64_t ls = readlane_u64(s, l), le = readlane_u64(e, l);
+            const uint64_t lk = ls + readlane_u64(kb, l); // the kept bytes end, the new ones begin
+            // the kept bytes, clipped to the tile
+            uint64_t w0 = ls > x0 ? ls : x0, w1 = min_u64(lk, x1);
+            if (w0 < w1)
+                wave_move(A.out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(ksrc, l)) + (w0 - ls), static_cast<uint32_t>(w1 - w0),
+                          t);
+            w0 = lk > x0 ? lk : x0, w1 = min_u64(le, x1);
+            if (w0 < w1)
+                wave_move(A.out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(nsrc, l)) + (w0 - lk), static_cast<uint32_t>(w1 - w0),
+                          t);
+        }
+        // the batch's end: past the tile, or the last list
+        const uint64_t be = jb + 64u <= n ? A.lstart[jb + 64u] : total;
+        if (jb + 64u >= n || be >= x1)
+            break;
+        jb += 64u;
+    }
+}
+
+} // namespace tpf::dev
+
+namespace tpf
+{
+
+namespace
+{
+size_t al256a(size_t x) { return (x + 255u) & ~size_t(255); }
+
+uint64_t app_runs(uint64_t n) { return (n + 63u) / 64u; }
+
+// Capacities of the staging, from the sizes alone: at most T lists receive
+// values, at most Tt of them have an old tail (<= 255 values each), and a list
+// that receives a values is staged as at most a / 256 + 2 units.
+struct AppCaps
+{
+    uint64_t T, Tt, vals, units, bytes;
+    AppCaps(uint64_t nunits, uint64_t n, uint64_t add_values)
+    {
+        T = std::min(n, add_values);
+        Tt = std::min(T, nunits);
+        vals = add_values + 255u * Tt;
+        units = add_values / 256u + 2u * T + 1u; // never 0: the encoder's passes always run
+        bytes = tpf_p4nenc256v32_lists_bound(vals, T);
+    }
+};
+
+// Workspace: header | four run scans over the lists' 64-runs | tv, m, db, sst
+// (n each) | sptr, kbpre, lstart (n + 1 each, u64) | staged values | staged
+// units' offsets | staged bytes (+ 16: the stitch reads whole dwords) | the
+// encoder's workspace, each 256-byte aligned.
+struct AppWs
+{
+    dev::AppHdr * hdr;
+    RunScanWs<uint64_t> stv, stt, sm, sdb;
+    uint32_t *tv, *m, *db, *sst, *stage;
+    uint64_t *sptr, *kbpre, *lstart, *noff;
+    uint8_t * sbytes;
+    void * enc;
+    size_t bytes;
+
+    AppWs(void * ws, uint64_t n, const AppCaps & C)
+    {
+        auto * p = static_cast<uint8_t *>(ws);
+        size_t x = 0;
+        hdr = reinterpret_cast<dev::AppHdr *>(p + x);
+        x += 256u;
+        const uint64_t nr = app_runs(n);
+        for (RunScanWs<uint64_t> * s : {&stv, &stt, &sm, &sdb})
+        {
+            *s = RunScanWs<uint64_t>::carve(p + x, nr);
+            x += al256a(RunScanWs<uint64_t>::bytes(nr));
+        }
+        for (uint32_t ** a : {&tv, &m, &db, &sst})
+        {
+            *a = reinterpret_cast<uint32_t *>(p + x);
+            x += al256a(4u * n);
+        }
+        for (uint64_t ** a : {&sptr, &kbpre, &lstart})
+        {
+            *a = reinterpret_cast<uint64_t *>(p + x);
+            x += al256a(8u * (n + 1u));
+        }
+        stage = reinterpret_cast<uint32_t *>(p + x);
+        x += al256a(4u * C.vals);
+        noff = reinterpret_cast<uint64_t *>(p + x);
+        x += al256a(8u * (C.units + 1u));
+        sbytes = p + x;
+        x += al256a(C.bytes + 16u);
+        enc = p + x;
+        x += al256a(lists_enc_workspace(C.units, n));
+        bytes = x;
+    }
+};
+} // namespace
+
+size_t lists_append_workspace(uint64_t nunits, uint64_t nlists_out, uint64_t add_values)
+{
+    if (nlists_out == 0)
+        return 0;
+    return AppWs(nullptr, nlists_out, AppCaps(nunits, nlists_out, add_values)).bytes;
+}
+
+// Launches, fixed by the sizes: reset, plan, 4 x 2 run scans, heads, [stage
+// additions, stage tails,] 6 of the encoder, segs, [offsets,] [stitch] -- 22
+// at the most, 23 with d_err's reset by the entry point.
+hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
+                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
+                               const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t n, uint8_t * out,
+                               uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out,
+                               uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s)
+{
+    hipError_t e;
+    const uint64_t ebase = nunits;
+    if (n == 0)
+    {
+        hipLaunchKernelGGL(dev::k_app_empty, dim3(1), dim3(64), 0, s, lptr_out, lunit_out, off_out);
+        return hipGetLastError();
+    }
+    if (nunits == 0 || nlists == 0) // an empty old index
+        nunits = 0, nlists = 0, in_bytes = 0;
+    const AppCaps C(nunits, n, add_values);
+    const AppWs W(ws, n, C);
+    const ListsEncPlanView V = lists_enc_plan_view(W.enc, C.units, n);
+    const dev::AppArgs A{in,        in_bytes,  off,        nunits,    lptr,      lunit,     nlists,     start0,    unit_last,
+                         add,       add_values, aptr,      n,         out,       out_cap,   off_out,    units_cap, lptr_out,
+                         lunit_out, ulast_out, err,        W.hdr,     W.stv.tot, W.stt.tot, W.sm.tot,   W.sdb.tot, W.stv.pre,
+                         W.stv.tile, W.stt.pre, W.stt.tile, W.sm.pre, W.sm.tile, W.sdb.pre, W.sdb.tile, W.tv,      W.m,
+                         W.db,      W.sst,     W.sptr,     W.kbpre,   W.lstart,  W.stage,   W.noff,     W.sbytes,  V.hdr,
+                         V.ubase,   V.rec,     C.units,   ebase};
+    auto grid = [](uint64_t items, uint64_t per) { return dim3(static_cast<uint32_t>((items + per - 1u) / per)); };
+    hipLaunchKernelGGL(dev::k_app_reset, dim3(1), dim3(64), 0, s, W.hdr, V.hdr);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_app_plan, grid(n, 256), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    const uint64_t nr = app_runs(n);
+    using u64p = uint64_t *;
+    if ((e = launch_run_scan_u64(W.stv.tot, nr, W.stv.pre, W.stv.tile, u64p(&W.hdr->tv), s)) != hipSuccess
+        || (e = launch_run_scan_u64(W.stt.tot, nr, W.stt.pre, W.stt.tile, u64p(&W.hdr->tt), s)) != hipSuccess
+        || (e = launch_run_scan_u64(W.sm.tot, nr, W.sm.pre, W.sm.tile, u64p(&W.hdr->m), s)) != hipSuccess
+        || (e = launch_run_scan_u64(W.sdb.tot, nr, W.sdb.pre, W.sdb.tile, u64p(&W.hdr->db), s)) != hipSuccess)
+        return e;
+    if (d1)
+        hipLaunchKernelGGL(dev::k_app_heads<true>, grid(n + 1u, 256), dim3(256), 0, s, A);
+    else
+        hipLaunchKernelGGL(dev::k_app_heads<false>, grid(n + 1u, 256), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if (add_values != 0u)
+    {
+        hipLaunchKernelGGL(dev::k_app_stage_add, grid(add_values, 256), dim3(256), 0, s, A);
+        if ((e = hipGetLastError()) != hipSuccess)
+            return e;
+        if (nlists != 0u)
+        {
+            const dim3 tg = grid(nlists, 4u * dev::kRunDefault);
+            if (d1)
+                hipLaunchKernelGGL((dev::k_app_stage_tails<true, dev::kTailsNC>), tg, dim3(256), 0, s, A);
+            else
+                hipLaunchKernelGGL((dev::k_app_stage_tails<false, dev::kTailsNC>), tg, dim3(256), 0, s, A);
+            if ((e = hipGetLastError()) != hipSuccess)
+                return e;
+        }
+    }
+    if ((e = launch_lists_enc_planned(W.stage, W.sptr, n, d1, d1 ? W.sst : nullptr, W.sbytes, C.bytes, W.noff, C.units, W.enc, s))
+        != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_app_segs, grid(n + 1u, 256), dim3(256), 0, s, A);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return e;
+    if (units_cap != 0u)
+    {
+        if (d1)
+            hipLaunchKernelGGL(dev::k_app_offsets<true>, grid(units_cap, 256), dim3(256), 0, s, A);
+        else
+            hipLaunchKernelGGL(dev::k_app_offsets<false>, grid(units_cap, 256), dim3(256), 0, s, A);
+        if ((e = hipGetLastError()) != hipSuccess)
+            return e;
+    }
+    // the stream is never longer than the old bytes plus the staged ones
+    const uint64_t span = std::min(out_cap, in_bytes + C.bytes);
+    if (span != 0u)
+    {
+        hipLaunchKernelGGL(dev::k_app_stitch, grid(span, 4u * dev::kListsAppendTile), dim3(256), 0, s, A);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+} // namespace tpf

@@ -56,7 +56,18 @@ struct ListsEncArgs
     uint64_t out_cap;
     uint64_t * off;
     unsigned long long * err;
+    uint32_t devn; // 1: nunits is a capacity and the unit count is hdr->h.total (the append, p4_lists_append.hip)
 };
+
+// The arguments with the unit count the kernels work on: the caller's, or the
+// one a device-side plan left in the header (more than the capacity: no go).
+__device__ __forceinline__ ListsEncArgs enc_args(const ListsEncArgs & K)
+{
+    ListsEncArgs A = K;
+    if (K.devn != 0u)
+        A.nunits = min_u64(K.hdr->h.total, K.nunits + 1u);
+    return A;
+}
 
 // A wave's run of up to kLencRun consecutive units: lane t holds unit first+t.
 // The full blocks' values are one contiguous input range (the tails' values
@@ -143,16 +154,22 @@ struct UnitRun
 
 // ---- full blocks: plan --------------------------------------------------------
 template <bool D1>
-__global__ __launch_bounds__(256) void k_lenc_plan(const ListsEncArgs A)
+__global__ __launch_bounds__(256) void k_lenc_plan(const ListsEncArgs K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][kPlanHistU32];
+    const ListsEncArgs A = enc_args(K);
     if (!lists_go(&A.hdr->h, A.nunits))
         return;
     const uint32_t t = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kLencRun;
     if (first >= A.nunits)
+    {
+        // a capacity's runs past the stream's end count nothing
+        if (K.devn != 0u && first < K.nunits && t == 0u)
+            A.run_tot[first / kLencRun] = 0u;
         return;
+    }
     UnitRun R;
     R.init(A, first, t);
     // a tail's size: left by the tails plan pass (an earlier kernel)
@@ -189,10 +206,11 @@ __global__ __launch_bounds__(256) void k_lenc_plan(const ListsEncArgs A)
 // a sub-run is out of the descriptor's range and every shared chunk is written
 // byte by byte.
 template <bool D1>
-__global__ __launch_bounds__(256) void k_lenc_write(const ListsEncArgs A)
+__global__ __launch_bounds__(256) void k_lenc_write(const ListsEncArgs K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t img_all[4][kImgU32];
     __shared__ __attribute__((aligned(16))) uint32_t val_all[4][kEncValU32];
+    const ListsEncArgs A = enc_args(K);
     if (!lists_go(&A.hdr->h, A.nunits))
         return;
     const uint32_t t = threadIdx.x & 63u;
@@ -267,10 +285,11 @@ __global__ __launch_bounds__(256) void k_lenc_write(const ListsEncArgs A)
 // k_enc_gr's dword loop with byte stores on the two edge dwords, which the
 // full blocks on either side share.
 template <bool D1, bool WRITE>
-__global__ __launch_bounds__(256) void k_lenc_tails(const ListsEncArgs A)
+__global__ __launch_bounds__(256) void k_lenc_tails(const ListsEncArgs K)
 {
     __shared__ __attribute__((aligned(16))) uint32_t imgs[WRITE ? 4 : 1][WRITE ? kLencTailImgU32 : 1];
     __shared__ __attribute__((aligned(16))) uint32_t hist[WRITE ? 1 : 4][WRITE ? 4 : kPlanGHistU32]; // plan pass only
+    const ListsEncArgs A = enc_args(K);
     if (!lists_go(&A.hdr->h, A.nunits))
         return;
     if constexpr (WRITE)
@@ -464,28 +483,11 @@ struct ListsEncWs
 
 size_t lists_enc_workspace(uint64_t nunits, uint64_t nlists) { return ListsEncWs(nullptr, nunits, nlists).bytes; }
 
-// 11 launches whatever the lists: header reset, plan, 2 x run scan, heads
-// (launch_lists_structure), tails plan, full plan, 2 x run scan, full write,
-// tails write -- 12 with d_err's reset by the entry point.
-hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint64_t * ptr, uint64_t nlists, bool d1,
-                            const uint32_t * start0, uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t nunits, void * ws,
-                            unsigned long long * err, hipStream_t s)
+// the passes after the structure: tails plan, full plan, run scan, full write, tails write
+static hipError_t lists_enc_passes(const dev::ListsEncArgs & A, const ListsEncWs & W, bool d1, hipStream_t s)
 {
-    if (nlists == 0)
-        return off != nullptr ? fill_u32(off, 0u, 2, s) : hipSuccess;
-    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    const ListsEncWs W(ws, nunits, nlists);
-    hipError_t e = launch_lists_structure(ptr, nlists, in_values, nunits, &W.hdr->h, W.lscan, W.ubase, W.rec, err, s);
-    if (e != hipSuccess)
-        return e;
-    if (nunits == 0)
-    {
-        hipLaunchKernelGGL(dev::k_lenc_empty, dim3(1), dim3(64), 0, s, W.hdr, off);
-        return hipGetLastError();
-    }
-    const dev::ListsEncArgs A{in, ptr, nlists, start0, nunits, W.hdr, W.rec, W.ubase, W.sz, W.plan, W.uscan.tot, W.uscan.pre,
-                              W.uscan.tile, out, out_cap, off, err};
+    hipError_t e;
+    const uint64_t nunits = A.nunits, nlists = A.nlists;
     const uint32_t grid = static_cast<uint32_t>((nunits + 4u * dev::kLencRun - 1u) / (4u * dev::kLencRun));
     const uint32_t tgrid = static_cast<uint32_t>((nlists + 4u * dev::kLencTailRun - 1u) / (4u * dev::kLencTailRun));
     if (d1)
@@ -515,6 +517,50 @@ hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint6
     else
         hipLaunchKernelGGL((dev::k_lenc_tails<false, true>), dim3(tgrid), dim3(256), 0, s, A);
     return hipGetLastError();
+}
+
+// 11 launches whatever the lists: header reset, plan, 2 x run scan, heads
+// (launch_lists_structure), tails plan, full plan, 2 x run scan, full write,
+// tails write -- 12 with d_err's reset by the entry point.
+hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint64_t * ptr, uint64_t nlists, bool d1,
+                            const uint32_t * start0, uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t nunits, void * ws,
+                            unsigned long long * err, hipStream_t s)
+{
+    if (nlists == 0)
+        return off != nullptr ? fill_u32(off, 0u, 2, s) : hipSuccess;
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    const ListsEncWs W(ws, nunits, nlists);
+    hipError_t e = launch_lists_structure(ptr, nlists, in_values, nunits, &W.hdr->h, W.lscan, W.ubase, W.rec, err, s);
+    if (e != hipSuccess)
+        return e;
+    if (nunits == 0)
+    {
+        hipLaunchKernelGGL(dev::k_lenc_empty, dim3(1), dim3(64), 0, s, W.hdr, off);
+        return hipGetLastError();
+    }
+    const dev::ListsEncArgs A{in, ptr, nlists, start0, nunits, W.hdr, W.rec, W.ubase, W.sz, W.plan, W.uscan.tot, W.uscan.pre,
+                              W.uscan.tile, out, out_cap, off, err, 0u};
+    return lists_enc_passes(A, W, d1, s);
+}
+
+// The encode of lists whose structure a caller planned on the device (the
+// append's staged lists): the caller fills the header (bad, total), ubase
+// (nlists + 1) and the unit records of the view, units_cap (> 0) bounds the
+// unit count, and nothing is reported through d_err.  6 launches.
+ListsEncPlanView lists_enc_plan_view(void * ws, uint64_t units_cap, uint64_t nlists)
+{
+    const ListsEncWs W(ws, units_cap, nlists);
+    return ListsEncPlanView{&W.hdr->h, W.ubase, W.rec};
+}
+
+hipError_t launch_lists_enc_planned(const uint32_t * in, const uint64_t * ptr, uint64_t nlists, bool d1, const uint32_t * start0,
+                                    uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t units_cap, void * ws, hipStream_t s)
+{
+    const ListsEncWs W(ws, units_cap, nlists);
+    const dev::ListsEncArgs A{in, ptr, nlists, start0, units_cap, W.hdr, W.rec, W.ubase, W.sz, W.plan, W.uscan.tot, W.uscan.pre,
+                              W.uscan.tile, out, out_cap, off, nullptr, 1u};
+    return lists_enc_passes(A, W, d1, s);
 }
 
 } // namespace tpf

@@ -174,6 +174,16 @@ def lib():
             L.tpf_lists_gather.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp,
                                            c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_lists_gather.restype = ctypes.c_int
+        if hasattr(L, "tpf_lists_append"):
+            L.tpf_lists_append_units_bound.argtypes = [c_u64, c_u64, c_u64]
+            L.tpf_lists_append_units_bound.restype = c_u64
+            L.tpf_lists_append_bound.argtypes = [c_u64, c_u64, c_u64]
+            L.tpf_lists_append_bound.restype = c_u64
+            L.tpf_lists_append_workspace_size.argtypes = [c_u64, c_u64, c_u64]
+            L.tpf_lists_append_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_append.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_u64,
+                                           c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_append.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -829,3 +839,70 @@ def lists_gather(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, d1=F
                               _ptr(start0), _ptr(unit_last), _ptr(pos), pos.numel(), _ptr(pos_ptr), _ptr(qlist), nq, _ptr(out), _ptr(ws),
                               ws.numel(), _ptr(err), _stream(torch)))
     return out
+
+
+# ---- postings appended to a resident index (include/turbopfor_gpu.h tpf_lists_append) ----
+LISTS_APPEND_TILE = 16384  # bytes of the output one wave of the append's stitch pass moves
+
+
+def lists_append_units_bound(nunits, nlists_out, add_values):
+    """A unit capacity that always suffices for lists_append
+    (tpf_lists_append_units_bound: advice, not a precondition)."""
+    return int(lib().tpf_lists_append_units_bound(int(nunits), int(nlists_out), int(add_values)))
+
+
+def lists_append_bound(in_bytes, nlists_out, add_values):
+    """A byte capacity that always suffices for lists_append
+    (tpf_lists_append_bound: advice, not a precondition)."""
+    return int(lib().tpf_lists_append_bound(int(in_bytes), int(nlists_out), int(add_values)))
+
+
+def lists_append(packed, offsets, list_ptr, list_unit, add, add_ptr, d1=False, start0=None, unit_last=None, nlists=None, out=None,
+                 out_offsets=None, units_cap=None, err=None, ws=None, stream=None):
+    """Append postings to the lists of a resident index, out of place: list j
+    of the result is the old list j followed by add[add_ptr[j]:add_ptr[j+1]].
+    packed / offsets / list_ptr / list_unit / start0 / unit_last: the old
+    index as decn256v32_lists_units reads it (unit_last required with d1); any
+    of the first four may be None for an empty old index.  nlists: the old
+    index's list count (default: list_ptr.numel() - 1); add_ptr: int64 CUDA
+    tensor [nlists_out + 1], nlists_out >= nlists -- lists past the old index
+    are new; start0 has nlists_out entries.  add: int32 CUDA tensor.  Full
+    blocks of the old stream are moved as bytes; only the tail of a list that
+    receives values is decoded and encoded again, so the result is byte for
+    byte encn256v32_lists of the concatenated lists.  out: uint8 CUDA tensor
+    whose numel() is the byte capacity (default: lists_append_bound);
+    out_offsets: int64 CUDA tensor [units_cap + 1] (default units_cap:
+    lists_append_units_bound, or out_offsets.numel() - 1).  err: optional
+    int64 CUDA tensor [1] (-1 = clean).  stream: a raw HIP stream handle
+    (default: torch's current stream).  Asynchronous: no device-to-host
+    read; the stream's length is out_offsets[list_unit_out[-1]].  Returns
+    (out, out_offsets, list_ptr_out, list_unit_out, unit_last_out or None)."""
+    import torch
+
+    if d1 and unit_last is None and packed is not None and offsets is not None and offsets.numel() > 1:
+        raise ValueError("lists_append: d1=True needs unit_last (lists_unit_last)")
+    dev = add_ptr.device
+    if nlists is None:
+        nlists = list_ptr.numel() - 1 if list_ptr is not None else 0
+    nunits = offsets.numel() - 1 if offsets is not None and nlists > 0 else 0
+    in_bytes = packed.numel() if packed is not None else 0
+    nlists_out = add_ptr.numel() - 1
+    nadd = add.numel() if add is not None else 0
+    L = lib()
+    if units_cap is None:
+        units_cap = out_offsets.numel() - 1 if out_offsets is not None else lists_append_units_bound(nunits, nlists_out, nadd)
+    if out_offsets is None:
+        out_offsets = torch.empty(units_cap + 1, dtype=torch.int64, device=dev)
+    if out is None:
+        out = torch.empty(max(lists_append_bound(in_bytes, nlists_out, nadd), 1), dtype=torch.uint8, device=dev)
+    list_ptr_out = torch.empty(nlists_out + 1, dtype=torch.int64, device=dev)
+    list_unit_out = torch.empty(nlists_out + 1, dtype=torch.int32, device=dev)
+    unit_last_out = torch.empty(max(units_cap, 1), dtype=torch.int32, device=dev) if d1 else None
+    ws_bytes = int(L.tpf_lists_append_workspace_size(nunits, nlists_out, nadd))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _check(L.tpf_lists_append(_ptr(packed), in_bytes, _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
+                              _ptr(start0), _ptr(unit_last), _ptr(add), nadd, _ptr(add_ptr), nlists_out, _ptr(out), out.numel(),
+                              _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out), _ptr(ws),
+                              ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
+    return out, out_offsets, list_ptr_out, list_unit_out, unit_last_out
