@@ -1,6 +1,7 @@
 // p4_dec_run.h -- per-wave run machinery shared by the 256v32 decode kernels
-// (p4_dec256v32.hip, p4_d1chain.hip): the run's control plane held in vector
-// lanes, the register-chunk loads and the LDS staging of one block.
+// (p4_dec256v32.hip, p4_d1chain.hip) and the lists kernels (p4_lists*.hip): the
+// run's control plane held in vector lanes, the register-chunk loads, the LDS
+// staging of one block and (the lists kernels) the rotating pipeline loop.
 #pragma once
 
 #include "p4_block32.h"
@@ -183,5 +184,51 @@ struct RunPlaneT
 };
 
 using RunPlane = RunPlaneT<kSlotBytes>;
+
+// The rotating issue / consume loop of a wave's run: NC entries of C in
+// registers, the load of item j + NC - 1 issued before item j is consumed,
+// the ring index a compile-time constant on every path.  Items past the run
+// are loaded too (load() yields nothing for them: one vmcnt pattern).  Two
+// calls, since some kernels put dependent gathers between priming and
+// draining, where they overlap the first loads.
+template <uint32_t NC, class E, class Load>
+__device__ __forceinline__ void ring_prime(E (&C)[NC], Load && load)
+{
+#pragma unroll
+    for (uint32_t q = 0; q + 1 < NC; ++q)
+        load(C[q], q);
+}
+
+template <uint32_t NC, class E, class Load, class Consume>
+__device__ __forceinline__ void ring_drain(E (&C)[NC], uint32_t n, Load && load, Consume && consume)
+{
+    bool more = true;
+    for (uint32_t j = 0; more; j += NC)
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < NC; ++q)
+        {
+            if (more)
+            {
+                load(C[(q + NC - 1) % NC], j + q + NC - 1);
+                consume(C[q], j + q);
+                more = j + q + 1 < n;
+            }
+        }
+    }
+}
+
+// the ring over a run plane's chunks: consume(chunk, jj) for jj = 0 .. n - 1
+template <uint32_t NC, class Plane>
+__device__ __forceinline__ void pipe_prime(const Plane & P, Chunk (&C)[NC], uint32_t t)
+{
+    ring_prime<NC>(C, [&](Chunk & c, uint32_t jj) { P.template issue<0>(c, jj, t); });
+}
+
+template <uint32_t NC, class Plane, class Consume>
+__device__ __forceinline__ void pipe_drain(const Plane & P, Chunk (&C)[NC], uint32_t n, uint32_t t, Consume && consume)
+{
+    ring_drain<NC>(C, n, [&](Chunk & c, uint32_t jj) { P.template issue<0>(c, jj, t); }, consume);
+}
 
 } // namespace tpf::dev

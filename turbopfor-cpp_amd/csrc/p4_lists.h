@@ -8,7 +8,8 @@
 // (k_dsum256v32_lists, p4_dec256v32.hip), its run scan, one prefix per list]
 // -> decode (k_lists_dec).  Nothing comes back to the host in between: every
 // kernel after the plan reads the header below and does nothing when the list
-// structure was refused.
+// structure was refused.  The device helpers the lists kernels share are in
+// p4_lists_dev.h, the host ones (workspace carver, grids) in p4_lists_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,6 +39,38 @@ __device__ __forceinline__ bool lists_go(const ListsHdr * h, uint64_t nunits)
 {
     return h->bad == ~0ull && h->total == nunits;
 }
+
+// Header of a decode over a SELECTION of a resident index's lists or unit
+// ranges (p4_lists_select.hip, p4_lists_units.hip).
+struct SelHdr
+{
+    unsigned long long bad;    // first refused selection k (~0: none)
+    unsigned long long vtotal; // virtual units: the sum of the selections' unit counts
+    unsigned long long ototal; // selected values: d_out_ptr[nsel]
+};
+
+// go / no-go: every selection is sound and the selected values fit the output
+// (then vtotal <= vcap follows, n values holding at most n/256 + 1 units; it
+// is checked all the same: vcap sizes the records and the sums)
+__device__ __forceinline__ bool sel_go(const SelHdr * h, uint64_t out_values, uint64_t vcap)
+{
+    return h->bad == ~0ull && h->ototal <= out_values && h->vtotal <= vcap;
+}
+
+// Header of a request served item by item (p4_lists_items.hip: the
+// intersection and the gather).  An ITEM is a run of consecutive request
+// indices that name one list and one source unit.
+struct ItemHdr
+{
+    unsigned long long bad; // first refused query k, or a code past nq of the entry's own (~0: none)
+    uint32_t nitems;
+    uint32_t spare;         // the intersection: nhits = d_out_ptr[nq]
+};
+
+// go / no-go of everything after the plan: nothing was refused
+__device__ __forceinline__ bool items_go(const ItemHdr * h) { return h->bad == ~0ull; }
+
+constexpr uint32_t kItemNone = 0xFFFFFFFFu; // unit word / list word: the request index names nothing
 
 } // namespace tpf::dev
 
@@ -103,6 +136,12 @@ size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists);
 hipError_t launch_lists_unit_last(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                                   uint64_t nlists, const uint32_t * start0, uint32_t * unit_last, void * ws, unsigned long long * err,
                                   hipStream_t s);
+// the passes the selective decode and the units decode share after their plan
+// kernels (p4_lists_select.hip): the two run scans (hdr->vtotal, hdr->ototal)
+// and the heads (the verdict, d_out_ptr, vbase, the virtual units' records)
+hipError_t launch_sel_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap, dev::SelHdr * hdr,
+                            const RunScanWs<uint64_t> & scanu, const uint64_t * totv, uint64_t * prev, uint64_t * tilev, uint32_t * vbase,
+                            uint32_t * rec, uint64_t * out_ptr, unsigned long long * err, hipStream_t s);
 hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t * unit_last, uint64_t nlists, uint64_t nunits,
                                     const uint32_t * qlist, const uint32_t * qlo, const uint32_t * qhi, uint64_t nq, uint32_t * ufirst,
                                     uint32_t * ucount, unsigned long long * err, hipStream_t s);
@@ -124,9 +163,15 @@ hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const u
                                   const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
                                   uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
                                   uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
-// the run scan (p4_scan.h) over a request's 64-index runs: one launch while the
-// run totals fit one tile, launch_run_scan_u32's two beyond (p4_lists_intersect.hip)
-hipError_t ix_scan(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total, hipStream_t s);
+// the item layer the intersection and the gather share (p4_lists_items.hip).  pu / pl: per request index
+// its source unit | kRecTail and its list, or kItemNone (the entry's plan).
+// launch_items_reset: d_err and the header's verdict in one launch.
+// launch_items: item heads (res != nullptr: every result word starts as
+// kItemNone) -> run scan of the 64-index runs (hdr->nitems) -> items (ihead /
+// iend: every item's first request index and one past its last).
+hipError_t launch_items_reset(unsigned long long * err, dev::ItemHdr * hdr, hipStream_t s);
+hipError_t launch_items(uint64_t pv, dev::ItemHdr * hdr, const uint32_t * pu, const uint32_t * pl, const RunScanWs<uint32_t> & scan,
+                        uint32_t * ihead, uint32_t * iend, uint32_t * res, hipStream_t s);
 // values at given list positions of a resident index (p4_lists_gather.hip;
 // DESIGN.md 4.12): the intersection's positional twin, for delta-1 and plain
 // streams.  Passes: plan (one thread per query: the checks; one per request

@@ -7,9 +7,7 @@
 
 #include "p4_dec256v32.h"
 #include "p4_lists_dev.h"
-#include "p4_generic.h"
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 
 namespace tpf::dev
 {
@@ -130,17 +128,14 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
     if (!lists_go(A.hdr, A.nunits))
         return;
     constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    uint32_t * scr = scratch[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, A.nunits);
+    const uint32_t t = R.t;
+    const uint64_t first = R.first;
     if (first >= A.nunits)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nunits - first));
-    const bool valid = t < n;
+    uint32_t * slot = slots[R.wv];
+    uint32_t * scr = scratch[R.wv];
+    const bool valid = t < R.n;
     const uint64_t u = first + t;
     const uint32_t r = valid ? A.rec[u] : 0u;
     const bool full = valid && (r & kRecTail) == 0u;
@@ -150,14 +145,12 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
     const uint64_t o = full ? A.off[u] : 0ull;
     const uint64_t e = full ? A.off[u + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
-    P.init(in_base, in_end, o, e, full);
+    P.init(R.in_base, R.in_end, o, e, full);
     // the first NC - 1 units' bytes go in flight before the list plane's
     // dependent gathers (rec -> list -> ubase / ptr / start0), which then
     // overlap them: a wave lives for 16 units only
     Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
+    pipe_prime<NC>(P, C, t);
 
     // ---- the list of every unit: heads inside the run, the search before it
     const uint32_t r0 = rl(r, 0) & kRecList;
@@ -189,36 +182,15 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
     }
 
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((fullmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         u32x4 v;
-        const uint32_t used = decode_block256v32(slot, (ctl >> kCtlShift) & 15u, P.head(c, ctl, slot), scr, t, v);
-        if constexpr (D1)
-            apply_delta1_256(v, rl(startv, jj));
+        decode_full_unit<D1>(P, c, jj, slot, scr, rl(startv, jj), t, v, badmask);
         st16_run(ors, rl(rel, jj) + 16u * t, v);
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-
-    bool more = true;
-    for (uint32_t j = 0; more; j += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], j + q + NC - 1, t);
-                consume(C[q], j + q);
-                more = j + q + 1 < n;
-            }
-        }
-    }
-    if (A.err != nullptr && t == 0 && badmask != 0u)
-        atomicMin(A.err, static_cast<unsigned long long>(first + __builtin_ctzll(badmask)));
+    });
+    report_bad_units(A.err, badmask, static_cast<uint32_t>(u), t);
 }
 
 // Decode of the tails: every wave owns kRunDefault consecutive LISTS with the
@@ -236,19 +208,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_li
     __shared__ uint32_t scratch[4][kListScratchU32];
     if (!lists_go(A.hdr, A.nunits))
         return;
-    constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
-    if (first >= A.nlists)
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const uint32_t t = R.t;
+    if (R.first >= A.nlists)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nlists - first));
-    const uint64_t j = first + t;
-    const uint64_t p0 = t < n ? A.ptr[j] : 0ull;
-    const uint64_t p1 = t < n ? A.ptr[j + 1u] : 0ull;
+    uint32_t * slot = slots[R.wv];
+    const uint64_t j = R.first + t;
+    const uint64_t p0 = t < R.n ? A.ptr[j] : 0ull;
+    const uint64_t p1 = t < R.n ? A.ptr[j + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
@@ -258,51 +225,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_li
     const uint64_t o = has ? A.off[u] : 0ull;
     const uint64_t e = has ? A.off[u + 1u] : 0ull;
     RunPlaneT<kListSlot> P;
-    P.init(in_base, in_end, o, e, has);
+    P.init(R.in_base, R.in_end, o, e, has);
     const uint64_t opos = p1 - cnt;
     uint32_t startv = 0u;
     if constexpr (D1)
         startv = has ? (A.start0 != nullptr ? A.start0[j] : 0u) + A.pbase[j + 1u] - A.pbase[j] : 0u;
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((hasmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         const uint32_t cj = rl(cnt, jj);
-        uint32_t v[4], cm;
-        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, v, &cm);
-        if constexpr (D1)
-            (void)delta1_g<uint32_t>(v, cj, rl(startv, jj), t);
+        TailVals v;
+        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, v, badmask);
         uint32_t * op = A.out + readlane_u64(opos, jj);
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
             if (t + 64u * q < cj)
-                __builtin_nontemporal_store(v[q], op + t + 64u * q);
+                __builtin_nontemporal_store(v.v[q], op + t + 64u * q);
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-    Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
-    bool more = true;
-    for (uint32_t jb = 0; more; jb += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
-                consume(C[q], jb + q);
-                more = jb + q + 1 < n;
-            }
-        }
-    }
-    // units ascend with the lists: the first bad lane is the lowest unit
-    if (A.err != nullptr && badmask != 0u && t == static_cast<uint32_t>(__builtin_ctzll(badmask)))
-        atomicMin(A.err, static_cast<unsigned long long>(u));
+    });
+    report_bad_units(A.err, badmask, u, t);
 }
 
 } // namespace tpf::dev
@@ -312,8 +256,6 @@ namespace tpf
 
 namespace
 {
-size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
-
 // Workspace: header | run scan of the lists' unit counts | ubase (nlists + 1)
 // | pbase (nlists + 1) | unit records (nunits) | phase A (the chained decode's
 // layout over nunits units), each 256-byte aligned.
@@ -327,28 +269,16 @@ struct ListsWs
 
     ListsWs(void * ws, uint64_t nunits, uint64_t nlists)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::ListsHdr *>(p + x);
-        x += 256u;
-        scan = RunScanWs<uint64_t>::carve(p + x, nlists);
-        x += al256(RunScanWs<uint64_t>::bytes(nlists));
-        ubase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nlists + 1u));
-        pbase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nlists + 1u));
-        rec = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * nunits);
-        chain = p + x;
-        x += al256(d1chain_workspace(nunits));
-        bytes = x;
+        WsCarver c(ws);
+        hdr = c.take<dev::ListsHdr>(1);
+        scan = c.scan<uint64_t>(nlists);
+        ubase = c.take<uint32_t>(nlists + 1u);
+        pbase = c.take<uint32_t>(nlists + 1u);
+        rec = c.take<uint32_t>(nunits);
+        chain = c.bytes<uint8_t>(d1chain_workspace(nunits));
+        bytes = c.used;
     }
 };
-
-uint32_t flat_grid(uint64_t items, hipStream_t s)
-{
-    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
-}
 } // namespace
 
 size_t lists_workspace(uint64_t nunits, uint64_t nlists) { return ListsWs(nullptr, nunits, nlists).bytes; }

@@ -27,8 +27,7 @@
 #include "p4_dec256v32.h"
 #include "p4_generic.h"
 #include "p4_lists_dev.h"
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 #include "turbopfor_gpu.h"
 
 #include <algorithm>
@@ -263,26 +262,9 @@ __global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
 }
 
 // ---- stage: the additions -----------------------------------------------------
-// The last j in [0, n) with tab[j] <= x, for tab[0] <= x < tab[n]: find_list's
-// cooperative search (p4_lists_dev.h) over 64-bit entries.
-template <class E>
-__device__ __forceinline__ uint32_t find_start(const E * __restrict tab, uint32_t n, uint64_t x, uint32_t t)
-{
-    uint32_t lo = 0u, hi = n;
-    while (hi - lo > 1u)
-    {
-        const uint32_t step = (hi - lo + 63u) / 64u;
-        const uint64_t p = static_cast<uint64_t>(lo) + static_cast<uint64_t>(t + 1u) * step;
-        const bool le = p < hi && tab[p] <= x;
-        const uint32_t c = static_cast<uint32_t>(__builtin_popcountll(__ballot(le)));
-        lo = uni(lo + c * step);
-        hi = uni(umin32(hi, lo + step));
-    }
-    return lo;
-}
-
-// The same for one lane, from a j0 known to be at or before the answer (the wave's first item's): a galloping search, one
-// probe when the item lies in list j0 as most do.
+// The last j in [0, n) with tab[j] <= x, for tab[0] <= x < tab[n]: find_list (p4_lists_dev.h) for the wave's first item,
+// then for one lane, from that j0 known to be at or before the answer, a galloping search -- one probe when the item
+// lies in list j0 as most do.
 template <class E>
 __device__ __forceinline__ uint32_t gallop(const E * __restrict tab, uint32_t n, uint32_t j0, uint64_t x)
 {
@@ -315,7 +297,7 @@ __global__ __launch_bounds__(256) void k_app_stage_add(const AppArgs A)
     if (pw >= end)
         return;
     // the last j with aptr[j] <= p (aptr[0] <= p < aptr[n]): the wave's first value by the cooperative search, the others from it
-    const uint32_t j0 = find_start(A.aptr, static_cast<uint32_t>(A.n), pw, t);
+    const uint32_t j0 = find_list(A.aptr, static_cast<uint32_t>(A.n), pw, t);
     if (i >= A.add_values || p >= end)
         return;
     const uint32_t lo = gallop(A.aptr, static_cast<uint32_t>(A.n), j0, p);
@@ -333,18 +315,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ap
     __shared__ uint32_t scratch[4][kListScratchU32];
     if (A.hdr->go == 0u)
         return;
-    constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
-    if (first >= A.nlists)
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const uint32_t t = R.t;
+    if (R.first >= A.nlists)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nlists - first));
-    const uint64_t k = first + t;
-    const uint32_t cnt = t < n ? A.tv[k] : 0u;
+    uint32_t * slot = slots[R.wv];
+    const uint64_t k = R.first + t;
+    const uint32_t cnt = t < R.n ? A.tv[k] : 0u;
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
     if (hasmask == 0ull)
@@ -353,7 +330,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ap
     const uint64_t o = has ? A.off[su] : 0ull;
     const uint64_t e = has ? A.off[su + 1u] : 0ull;
     RunPlaneT<kListSlot> P;
-    P.init(in_base, in_end, o, e, has);
+    P.init(R.in_base, R.in_end, o, e, has);
     const uint64_t opos = has ? A.sptr[k] : 0ull;
     uint32_t startv = 0u;
     if constexpr (D1)
@@ -362,48 +339,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ap
             startv = A.sst[k];
     }
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((hasmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         const uint32_t cj = rl(cnt, jj);
-        uint32_t x[4], cm;
-        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
-        if constexpr (D1)
-            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        TailVals x;
+        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
         uint32_t * op = A.stage + readlane_u64(opos, jj);
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
             if (t + 64u * q < cj)
-                op[t + 64u * q] = x[q];
+                op[t + 64u * q] = x.v[q];
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-    Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
-    bool more = true;
-    for (uint32_t jb = 0; more; jb += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
-                consume(C[q], jb + q);
-                more = jb + q + 1 < n;
-            }
-        }
-    }
-    if (A.err != nullptr && badmask != 0u)
-    {
-        const uint32_t mn = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
-        if (t == 0)
-            atomicMin(A.err, static_cast<unsigned long long>(mn));
-    }
+    });
+    report_bad_units(A.err, badmask, su, t);
 }
 
 // ---- segs: where every list's bytes start, and the capacity -----------------------
@@ -438,7 +389,7 @@ __global__ __launch_bounds__(256) void k_app_offsets(const AppArgs A)
     if (u - t >= nuo)
         return;
     // the last j with lunit_out[j] <= u (lunit_out[0] = 0 <= u < lunit_out[n]), as k_app_stage_add finds its list
-    const uint32_t j0 = find_start(A.lunit_out, static_cast<uint32_t>(A.n), u - t, t);
+    const uint32_t j0 = find_list(A.lunit_out, static_cast<uint32_t>(A.n), static_cast<uint32_t>(u - t), t); // u - t < nuo < 2^31
     if (u >= nuo)
         return;
     const uint64_t j = gallop(A.lunit_out, static_cast<uint32_t>(A.n), j0, u);
@@ -515,7 +466,7 @@ __global__ __launch_bounds__(256) void k_app_stitch(const AppArgs A)
     if (x0 >= total)
         return;
     const uint64_t x1 = min_u64(x0 + kListsAppendTile, total);
-    uint32_t jb = find_start(A.lstart, n, x0, t);
+    uint32_t jb = find_list(A.lstart, n, x0, t);
     for (;;)
     {
         // lane t: list jb + t, its bytes [s, e) of the output
@@ -584,8 +535,6 @@ namespace tpf
 
 namespace
 {
-size_t al256a(size_t x) { return (x + 255u) & ~size_t(255); }
-
 uint64_t app_runs(uint64_t n) { return (n + 63u) / 64u; }
 
 // Capacities of the staging, from the sizes alone: at most T lists receive
@@ -620,35 +569,19 @@ struct AppWs
 
     AppWs(void * ws, uint64_t n, const AppCaps & C)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::AppHdr *>(p + x);
-        x += 256u;
-        const uint64_t nr = app_runs(n);
+        WsCarver c(ws);
+        hdr = c.take<dev::AppHdr>(1);
         for (RunScanWs<uint64_t> * s : {&stv, &stt, &sm, &sdb})
-        {
-            *s = RunScanWs<uint64_t>::carve(p + x, nr);
-            x += al256a(RunScanWs<uint64_t>::bytes(nr));
-        }
+            *s = c.scan<uint64_t>(app_runs(n));
         for (uint32_t ** a : {&tv, &m, &db, &sst})
-        {
-            *a = reinterpret_cast<uint32_t *>(p + x);
-            x += al256a(4u * n);
-        }
+            *a = c.take<uint32_t>(n);
         for (uint64_t ** a : {&sptr, &kbpre, &lstart})
-        {
-            *a = reinterpret_cast<uint64_t *>(p + x);
-            x += al256a(8u * (n + 1u));
-        }
-        stage = reinterpret_cast<uint32_t *>(p + x);
-        x += al256a(4u * C.vals);
-        noff = reinterpret_cast<uint64_t *>(p + x);
-        x += al256a(8u * (C.units + 1u));
-        sbytes = p + x;
-        x += al256a(C.bytes + 16u);
-        enc = p + x;
-        x += al256a(lists_enc_workspace(C.units, n));
-        bytes = x;
+            *a = c.take<uint64_t>(n + 1u);
+        stage = c.take<uint32_t>(C.vals);
+        noff = c.take<uint64_t>(C.units + 1u);
+        sbytes = c.bytes<uint8_t>(C.bytes + 16u);
+        enc = c.bytes<uint8_t>(lists_enc_workspace(C.units, n));
+        bytes = c.used;
     }
 };
 } // namespace

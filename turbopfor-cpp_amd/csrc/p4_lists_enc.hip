@@ -20,8 +20,7 @@
 #include "p4_enc256v32.h"
 #include "p4_generic.h"
 #include "p4_lists_dev.h"
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 
 namespace tpf::dev
 {
@@ -129,26 +128,13 @@ struct UnitRun
     template <class Body>
     __device__ __forceinline__ void walk(uint32_t t, Body && body) const
     {
-        constexpr uint32_t NC = kLencNC;
-        u32x4 C[NC];
-#pragma unroll
-        for (uint32_t q = 0; q + 1 < NC; ++q)
-            C[q] = load(q, t);
-        bool more = true;
-        for (uint32_t j = 0; more; j += NC)
-        {
-#pragma unroll
-            for (uint32_t q = 0; q < NC; ++q)
-            {
-                if (more)
-                {
-                    C[(q + NC - 1) % NC] = load(j + q + NC - 1, t);
-                    if ((fullmask >> (j + q)) & 1ull)
-                        body(C[q], j + q);
-                    more = j + q + 1 < n;
-                }
-            }
-        }
+        u32x4 C[kLencNC];
+        const auto ld = [&](u32x4 & c, uint32_t jj) { c = load(jj, t); };
+        ring_prime<kLencNC>(C, ld);
+        ring_drain<kLencNC>(C, n, ld, [&](const u32x4 & c, uint32_t jj) {
+            if ((fullmask >> jj) & 1ull)
+                body(c, jj);
+        });
     }
 };
 
@@ -444,8 +430,6 @@ namespace tpf
 
 namespace
 {
-size_t al256e(size_t x) { return (x + 255u) & ~size_t(255); }
-
 uint64_t lenc_runs(uint64_t nunits) { return (nunits + dev::kLencRun - 1u) / dev::kLencRun; }
 
 // Workspace: header | run scan of the lists' unit counts | ubase (nlists + 1)
@@ -460,23 +444,15 @@ struct ListsEncWs
 
     ListsEncWs(void * ws, uint64_t nunits, uint64_t nlists)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::ListsEncHdr *>(p + x);
-        x += 256u;
-        lscan = RunScanWs<uint64_t>::carve(p + x, nlists);
-        x += al256e(RunScanWs<uint64_t>::bytes(nlists));
-        ubase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256e(4u * (nlists + 1u));
-        rec = reinterpret_cast<uint32_t *>(p + x);
-        x += al256e(4u * nunits);
-        sz = reinterpret_cast<uint32_t *>(p + x);
-        x += al256e(4u * nunits);
-        plan = reinterpret_cast<uint32_t *>(p + x);
-        x += al256e(4u * nunits);
-        uscan = RunScanWs<uint64_t>::carve(p + x, lenc_runs(nunits));
-        x += al256e(RunScanWs<uint64_t>::bytes(lenc_runs(nunits)));
-        bytes = x;
+        WsCarver c(ws);
+        hdr = c.take<dev::ListsEncHdr>(1);
+        lscan = c.scan<uint64_t>(nlists);
+        ubase = c.take<uint32_t>(nlists + 1u);
+        rec = c.take<uint32_t>(nunits);
+        sz = c.take<uint32_t>(nunits);
+        plan = c.take<uint32_t>(nunits);
+        uscan = c.scan<uint64_t>(lenc_runs(nunits));
+        bytes = c.used;
     }
 };
 } // namespace

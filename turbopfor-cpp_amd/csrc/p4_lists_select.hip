@@ -11,27 +11,10 @@
 
 #include "p4_dec256v32.h"
 #include "p4_lists_dev.h"
-#include "p4_generic.h"
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 
 namespace tpf::dev
 {
-
-struct SelHdr
-{
-    unsigned long long bad;    // first refused selection k (~0: none)
-    unsigned long long vtotal; // virtual units: the sum of the selections' unit counts
-    unsigned long long ototal; // selected values: d_out_ptr[nsel]
-};
-
-// go / no-go: every selection is sound and the selected values fit the output
-// (then vtotal <= vcap follows, a list of n values holding at most n/256 + 1
-// units; it is checked all the same: vcap sizes the records and the sums)
-__device__ __forceinline__ bool sel_go(const SelHdr * h, uint64_t out_values, uint64_t vcap)
-{
-    return h->bad == ~0ull && h->ototal <= out_values && h->vtotal <= vcap;
-}
 
 struct SelArgs
 {
@@ -105,23 +88,10 @@ __global__ __launch_bounds__(256) void k_sel_plan(const uint64_t * __restrict pt
     const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
     for (uint64_t k = gid; k < nsel; k += gsz)
     {
-        const uint32_t j = sel[k];
-        bool bad = j >= nlists;
-        uint64_t n = 0u;
-        uint32_t units = 0u;
-        if (!bad)
-        {
-            const uint64_t a = ptr[j], b = ptr[j + 1u];
-            const uint32_t ua = list_unit[j], ub = list_unit[j + 1u];
-            bad = b < a || ub < ua || ub > nunits;
-            if (!bad)
-            {
-                n = b - a;
-                units = list_units(n);
-                bad = ub - ua != units;
-            }
-        }
-        totu[k] = bad ? 0u : units;
+        uint64_t n;
+        uint32_t ua, ub;
+        const bool bad = !list_dir_ok(ptr, list_unit, nlists, nunits, sel[k], &n, &ua, &ub);
+        totu[k] = bad ? 0u : ub - ua;
         totv[k] = bad ? 0ull : n;
         if (bad)
             atomicMin(&hdr->bad, static_cast<unsigned long long>(k));
@@ -130,9 +100,12 @@ __global__ __launch_bounds__(256) void k_sel_plan(const uint64_t * __restrict pt
         rec[u] = 0u;
 }
 
-// Heads: the verdict (d_err for a refused selection or an output that is too
-// small), d_out_ptr, then per selection its virtual unit base and the records
-// of its first unit and of its tail -- the head carries k + 1, the SELECTION.
+// Heads (the selective decode and the units decode): the verdict (d_err for a
+// refused selection or an output that is too small), d_out_ptr, then per
+// selection its virtual unit base and the records of its first unit and of its
+// tail -- the head carries k + 1, the SELECTION.  A selection has a tail to
+// decode exactly when its value count is no multiple of 256: it reaches the
+// list's last unit and that unit is a p4Enc32 tail.
 __global__ __launch_bounds__(256) void k_sel_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap,
                                                     const uint32_t * __restrict totu, const uint64_t * __restrict totv,
                                                     const uint64_t * __restrict preu, const uint64_t * __restrict tileu,
@@ -228,14 +201,10 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
     constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    uint32_t * scr = scratch[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
     const uint64_t vt = A.hdr->vtotal;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, vt);
+    const uint32_t t = R.t, wv = R.wv;
+    const uint64_t first = R.first;
     if (first >= vt)
     {
         // the grid is sized by the host's cap: a wave past the real count has
@@ -244,8 +213,9 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
             A.run_tot[first / kRun] = 0u;
         return;
     }
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, vt - first));
-    const bool valid = t < n;
+    uint32_t * slot = slots[wv];
+    uint32_t * scr = scratch[wv];
+    const bool valid = t < R.n;
     const uint64_t v = first + t;
     const uint32_t r = valid ? A.rec[v] : 0u;
     const bool full = valid && (r & kRecTail) == 0u;
@@ -274,7 +244,7 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
     const uint64_t o = full ? A.off[su] : 0ull;
     const uint64_t e = full ? A.off[su + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
-    P.init(in_base, in_end, o, e, full);
+    P.init(R.in_base, R.in_end, o, e, full);
     if (!SUM && t < kRun)
         srcu[wv][t] = full ? su : 0xFFFFFFFFu;
 
@@ -301,47 +271,23 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
         }
     }
     Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
+    pipe_prime<NC>(P, C, t);
 
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((fullmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         u32x4 x;
-        const uint32_t used = decode_block256v32(slot, (ctl >> kCtlShift) & 15u, P.head(c, ctl, slot), scr, t, x);
+        decode_full_unit<D1 && !SUM>(P, c, jj, slot, scr, rl(startv, jj), t, x, badmask);
         if constexpr (SUM)
         {
             const uint32_t sm = wave_sum(x.x + x.y + x.z + x.w + 4u);
             sumv = t == jj ? sm : sumv;
         }
         else
-        {
-            if constexpr (D1)
-                apply_delta1_256(x, rl(startv, jj));
             st16_run(ors, rl(rel, jj) + 16u * t, x);
-        }
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-
-    bool more = true;
-    for (uint32_t j = 0; more; j += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], j + q + NC - 1, t);
-                consume(C[q], j + q);
-                more = j + q + 1 < n;
-            }
-        }
-    }
+    });
     if constexpr (SUM)
     {
         // the decode pass re-checks every unit: parse errors are reported there
@@ -350,13 +296,8 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
             A.sums[v] = sumv;
         publish_run_total(A.run_tot, first / kRun, sumv, t);
     }
-    else if (A.err != nullptr && badmask != 0u)
-    {
-        // in stream numbering; the source units of a run do not ascend
-        const uint32_t m = wave_min((t < kRun && ((badmask >> t) & 1ull) != 0ull) ? srcu[wv][t] : 0xFFFFFFFFu);
-        if (t == 0)
-            atomicMin(A.err, static_cast<unsigned long long>(m));
-    }
+    else
+        report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
 }
 
 // Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
@@ -372,19 +313,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_se
     __shared__ uint32_t scratch[4][kListScratchU32];
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
-    constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
-    if (first >= A.nsel)
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nsel);
+    const uint32_t t = R.t;
+    if (R.first >= A.nsel)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nsel - first));
-    const uint64_t k = first + t;
-    const uint64_t p0 = t < n ? A.out_ptr[k] : 0ull;
-    const uint64_t p1 = t < n ? A.out_ptr[k + 1u] : 0ull;
+    uint32_t * slot = slots[R.wv];
+    const uint64_t k = R.first + t;
+    const uint64_t p0 = t < R.n ? A.out_ptr[k] : 0ull;
+    const uint64_t p1 = t < R.n ? A.out_ptr[k + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
@@ -395,54 +331,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_se
     const uint64_t o = has ? A.off[su] : 0ull;
     const uint64_t e = has ? A.off[su + 1u] : 0ull;
     RunPlaneT<kListSlot> P;
-    P.init(in_base, in_end, o, e, has);
+    P.init(R.in_base, R.in_end, o, e, has);
     const uint64_t opos = p1 - cnt;
     uint32_t startv = 0u;
     if constexpr (D1)
         startv = has ? (A.start0 != nullptr ? A.start0[lj] : 0u) + A.pbase[k + 1u] - A.pbase[k] : 0u;
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((hasmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         const uint32_t cj = rl(cnt, jj);
-        uint32_t x[4], cm;
-        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
-        if constexpr (D1)
-            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        TailVals x;
+        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
         uint32_t * op = A.out + readlane_u64(opos, jj);
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
             if (t + 64u * q < cj)
-                __builtin_nontemporal_store(x[q], op + t + 64u * q);
+                __builtin_nontemporal_store(x.v[q], op + t + 64u * q);
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-    Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
-    bool more = true;
-    for (uint32_t jb = 0; more; jb += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
-                consume(C[q], jb + q);
-                more = jb + q + 1 < n;
-            }
-        }
-    }
-    if (A.err != nullptr && badmask != 0u)
-    {
-        const uint32_t m = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
-        if (t == 0)
-            atomicMin(A.err, static_cast<unsigned long long>(m));
-    }
+    });
+    report_bad_units(A.err, badmask, su, t);
 }
 
 } // namespace tpf::dev
@@ -452,55 +362,28 @@ namespace tpf
 
 namespace
 {
-size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
-
 uint64_t sel_runs(uint64_t vcap) { return (vcap + dev::kRunDefault - 1u) / dev::kRunDefault; }
 
-// Workspace of the selective decode: header | run scan of the selections'
-// unit counts | their value counts and that scan (u64) | vbase (nsel + 1) |
+// Workspace of the selective decode: the selection prefix (p4_lists_host.h) |
 // pbase (nsel + 1) | records of the virtual units (vcap) | block sums (vcap)
 // and the scan of their 16-unit run totals, each 256-byte aligned.
 struct SelWs
 {
-    dev::SelHdr * hdr;
-    RunScanWs<uint64_t> scanu;
-    uint64_t *totv, *prev, *tilev;
-    uint32_t *vbase, *pbase, *rec, *sums;
+    WsCarver c;
+    SelPlanWs plan;
+    uint32_t *pbase, *rec, *sums;
     RunScanWs<uint32_t> scans;
     size_t bytes;
 
-    SelWs(void * ws, uint64_t nsel, uint64_t vcap)
+    SelWs(void * ws, uint64_t nsel, uint64_t vcap) : c(ws), plan(c, nsel)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::SelHdr *>(p + x);
-        x += 256u;
-        scanu = RunScanWs<uint64_t>::carve(p + x, nsel);
-        x += al256(RunScanWs<uint64_t>::bytes(nsel));
-        totv = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * nsel);
-        prev = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * nsel);
-        tilev = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * RunScanWs<uint64_t>::tiles(nsel)) + 256u;
-        vbase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nsel + 1u));
-        pbase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nsel + 1u));
-        rec = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * vcap);
-        sums = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * vcap);
-        scans = RunScanWs<uint32_t>::carve(p + x, sel_runs(vcap));
-        x += al256(RunScanWs<uint32_t>::bytes(sel_runs(vcap)));
-        bytes = x;
+        pbase = c.take<uint32_t>(nsel + 1u);
+        rec = c.take<uint32_t>(vcap);
+        sums = c.take<uint32_t>(vcap);
+        scans = c.scan<uint32_t>(sel_runs(vcap));
+        bytes = c.used;
     }
 };
-
-uint32_t flat_grid(uint64_t items, hipStream_t s)
-{
-    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
-}
 } // namespace
 
 size_t lists_unit_base_workspace(uint64_t nlists) { return 256u + al256(RunScanWs<uint64_t>::bytes(nlists)); }
@@ -531,6 +414,20 @@ size_t lists_select_workspace(uint64_t nsel, uint64_t out_values)
     return SelWs(nullptr, nsel, lists_select_unit_cap(nsel, out_values)).bytes;
 }
 
+hipError_t launch_sel_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap, dev::SelHdr * hdr,
+                            const RunScanWs<uint64_t> & scanu, const uint64_t * totv, uint64_t * prev, uint64_t * tilev, uint32_t * vbase,
+                            uint32_t * rec, uint64_t * out_ptr, unsigned long long * err, hipStream_t s)
+{
+    hipError_t e;
+    if ((e = launch_run_scan_u64(scanu.tot, nsel, scanu.pre, scanu.tile, reinterpret_cast<uint64_t *>(&hdr->vtotal), s)) != hipSuccess)
+        return e;
+    if ((e = launch_run_scan_u64t(totv, nsel, prev, tilev, reinterpret_cast<uint64_t *>(&hdr->ototal), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::k_sel_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, scanu.tot, totv,
+                       scanu.pre, scanu.tile, prev, tilev, hdr, vbase, rec, out_ptr, err);
+    return hipGetLastError();
+}
+
 hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                                const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
                                uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
@@ -542,22 +439,18 @@ hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint
     if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const SelWs W(ws, nsel, vcap);
-    hipError_t e = fill_u32(W.hdr, 0xFFFFFFFFu, 2, s);
+    const SelPlanWs & S = W.plan;
+    hipError_t e = fill_u32(S.hdr, 0xFFFFFFFFu, 2, s);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(dev::k_sel_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, nsel,
-                       W.scanu.tot, W.totv, W.hdr, W.rec, vcap);
+                       S.scanu.tot, S.totv, S.hdr, W.rec, vcap);
     if ((e = hipGetLastError()) != hipSuccess)
         return e;
-    if ((e = launch_run_scan_u64(W.scanu.tot, nsel, W.scanu.pre, W.scanu.tile, reinterpret_cast<uint64_t *>(&W.hdr->vtotal), s)) != hipSuccess)
+    if ((e = launch_sel_heads(nsel, nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+        != hipSuccess)
         return e;
-    if ((e = launch_run_scan_u64t(W.totv, nsel, W.prev, W.tilev, reinterpret_cast<uint64_t *>(&W.hdr->ototal), s)) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(dev::k_sel_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, W.scanu.tot, W.totv,
-                       W.scanu.pre, W.scanu.tile, W.prev, W.tilev, W.hdr, W.vbase, W.rec, out_ptr, err);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    const dev::SelArgs A{in, in_bytes, off, list_unit, start0, sel, nsel, out, out_values, vcap, out_ptr, W.hdr, W.rec, W.vbase, W.pbase,
+    const dev::SelArgs A{in, in_bytes, off, list_unit, start0, sel, nsel, out, out_values, vcap, out_ptr, S.hdr, W.rec, S.vbase, W.pbase,
                          W.sums, W.scans.tot, W.scans.pre, W.scans.tile, err};
     // sized by the host's cap: waves past the real unit count exit
     const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));

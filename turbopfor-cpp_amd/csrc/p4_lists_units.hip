@@ -14,9 +14,7 @@
 
 #include "p4_dec256v32.h"
 #include "p4_lists_dev.h"
-#include "p4_generic.h"
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 
 namespace tpf::dev
 {
@@ -75,19 +73,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ul
     __shared__ uint32_t scratch[4][kListScratchU32];
     if (!lists_go(A.hdr, A.nunits))
         return;
-    constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
-    if (first >= A.nlists)
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const uint32_t t = R.t;
+    if (R.first >= A.nlists)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nlists - first));
-    const uint64_t j = first + t;
-    const uint64_t p0 = t < n ? A.ptr[j] : 0ull;
-    const uint64_t p1 = t < n ? A.ptr[j + 1u] : 0ull;
+    uint32_t * slot = slots[R.wv];
+    const uint64_t j = R.first + t;
+    const uint64_t p0 = t < R.n ? A.ptr[j] : 0ull;
+    const uint64_t p1 = t < R.n ? A.ptr[j + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
@@ -97,49 +90,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ul
     const uint64_t o = has ? A.off[u] : 0ull;
     const uint64_t e = has ? A.off[u + 1u] : 0ull;
     RunPlaneT<kListSlot> P;
-    P.init(in_base, in_end, o, e, has);
+    P.init(R.in_base, R.in_end, o, e, has);
     uint32_t sumv = 0u;
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((hasmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         const uint32_t cj = rl(cnt, jj);
-        uint32_t v[4], cm;
-        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, v, &cm);
+        TailVals v;
+        decode_tail_unit<false>(P, c, jj, slot, scratch[R.wv], cj, 0u, t, v, badmask);
         uint32_t loc = 0u;
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
-            loc += t + 64u * q < cj ? v[q] + 1u : 0u;
+            loc += t + 64u * q < cj ? v.v[q] + 1u : 0u;
         const uint32_t sm = wave_sum(loc);
         sumv = t == jj ? sm : sumv;
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-    Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
-    bool more = true;
-    for (uint32_t jb = 0; more; jb += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
-                consume(C[q], jb + q);
-                more = jb + q + 1 < n;
-            }
-        }
-    }
+    });
     if (has)
         A.tsum[j] = sumv;
-    // units ascend with the lists: the first bad lane is the lowest unit
-    if (A.err != nullptr && badmask != 0u && t == static_cast<uint32_t>(__builtin_ctzll(badmask)))
-        atomicMin(A.err, static_cast<unsigned long long>(u));
+    report_bad_units(A.err, badmask, u, t);
 }
 
 // The write pass: every wave owns one of phase A's 64-unit runs, lane t unit
@@ -232,21 +204,6 @@ __global__ __launch_bounds__(256) void k_range_units(const uint32_t * __restrict
 }
 
 // ---- the decode of unit ranges -------------------------------------------------
-struct UnHdr
-{
-    unsigned long long bad;    // first refused selection k (~0: none)
-    unsigned long long vtotal; // virtual units: the sum of the selections' unit counts
-    unsigned long long ototal; // selected values: d_out_ptr[nsel]
-};
-
-// go / no-go: every selection is sound and the selected values fit the output
-// (then vtotal <= vcap follows, a range of n values holding at most n/256 + 1
-// units; it is checked all the same: vcap sizes the records)
-__device__ __forceinline__ bool un_go(const UnHdr * h, uint64_t out_values, uint64_t vcap)
-{
-    return h->bad == ~0ull && h->ototal <= out_values && h->vtotal <= vcap;
-}
-
 struct UnArgs
 {
     const uint8_t * in;
@@ -263,7 +220,7 @@ struct UnArgs
     uint64_t out_values;
     uint64_t vcap;             // the host's cap on the virtual units: out_values / 256 + nsel
     const uint64_t * out_ptr;  // d_out_ptr (written by the heads pass)
-    const UnHdr * hdr;
+    const SelHdr * hdr;
     const uint32_t * rec;      // records of the virtual units (p4_lists.h)
     const uint32_t * vbase;    // first virtual unit of every selection, nsel + 1
     unsigned long long * err;
@@ -274,35 +231,29 @@ struct UnArgs
 // (the values are checked here, never followed) -- and the records of the
 // virtual units zeroed for the heads pass, up to the host's cap.  A range
 // holds 256 values per unit, but n % 256 in the list's p4Enc32 tail unit.
+// (k_sel_plan with the range arithmetic; the heads pass is k_sel_heads.)
 __global__ __launch_bounds__(256) void k_un_plan(const uint64_t * __restrict ptr, const uint32_t * __restrict list_unit, uint64_t nlists,
                                                   uint64_t nunits, const uint32_t * __restrict sel, const uint32_t * __restrict ufirst,
                                                   const uint32_t * __restrict ucount, uint64_t nsel, uint32_t * __restrict totu,
-                                                  uint64_t * __restrict totv, UnHdr * __restrict hdr, uint32_t * __restrict rec,
+                                                  uint64_t * __restrict totv, SelHdr * __restrict hdr, uint32_t * __restrict rec,
                                                   uint64_t vcap)
 {
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
     for (uint64_t k = gid; k < nsel; k += gsz)
     {
-        const uint32_t j = sel[k];
         const uint64_t uf = ufirst[k], uc = ucount[k];
-        bool bad = j >= nlists;
-        uint64_t nv = 0u;
+        uint64_t n, nv = 0u;
+        uint32_t ua, ub;
+        bool bad = !list_dir_ok(ptr, list_unit, nlists, nunits, sel[k], &n, &ua, &ub);
         if (!bad)
         {
-            const uint64_t a = ptr[j], b = ptr[j + 1u];
-            const uint32_t ua = list_unit[j], ub = list_unit[j + 1u];
-            bad = b < a || ub < ua || ub > nunits;
+            const uint32_t units = ub - ua;
+            bad = uf + uc > units; // 64-bit: the sum cannot wrap
             if (!bad)
             {
-                const uint64_t n = b - a;
-                const uint32_t units = list_units(n);
-                bad = ub - ua != units || uf + uc > units; // 64-bit: the sum cannot wrap
-                if (!bad)
-                {
-                    const uint32_t r = static_cast<uint32_t>(n & 255u);
-                    nv = 256u * uc - ((uc != 0u && uf + uc == units && r != 0u) ? 256u - r : 0u);
-                }
+                const uint32_t r = static_cast<uint32_t>(n & 255u);
+                nv = 256u * uc - ((uc != 0u && uf + uc == units && r != 0u) ? 256u - r : 0u);
             }
         }
         totu[k] = bad ? 0u : static_cast<uint32_t>(uc);
@@ -314,66 +265,15 @@ __global__ __launch_bounds__(256) void k_un_plan(const uint64_t * __restrict ptr
         rec[u] = 0u;
 }
 
-// Heads: the verdict (d_err for a refused selection or an output that is too
-// small), d_out_ptr, then per selection its virtual unit base and the records
-// of its first unit and of its tail -- the head carries k + 1, the SELECTION.
-// A range has a tail to decode exactly when its value count is no multiple of
-// 256: it reaches the list's last unit and that unit is a p4Enc32 tail.
-__global__ __launch_bounds__(256) void k_un_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values, uint64_t vcap,
-                                                   const uint32_t * __restrict totu, const uint64_t * __restrict totv,
-                                                   const uint64_t * __restrict preu, const uint64_t * __restrict tileu,
-                                                   const uint64_t * __restrict prev, const uint64_t * __restrict tilev,
-                                                   const UnHdr * __restrict hdr, uint32_t * __restrict vbase, uint32_t * __restrict rec,
-                                                   uint64_t * __restrict out_ptr, unsigned long long * __restrict err)
-{
-    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
-    const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
-    if (hdr->bad != ~0ull)
-    {
-        if (gid == 0 && err != nullptr)
-            *err = nunits + hdr->bad;
-        return;
-    }
-    const bool go = un_go(hdr, out_values, vcap);
-    for (uint64_t k = gid; k < nsel; k += gsz)
-        out_ptr[k] = run_base(prev, tilev, k);
-    if (gid == 0)
-    {
-        out_ptr[nsel] = hdr->ototal;
-        if (!go && err != nullptr)
-            *err = nunits + nsel;
-    }
-    if (!go)
-        return;
-    for (uint64_t k = gid; k < nsel; k += gsz)
-    {
-        const uint32_t vb = static_cast<uint32_t>(run_base(preu, tileu, k)); // <= vtotal <= vcap < 2^31
-        vbase[k] = vb;
-        const uint32_t units = totu[k];
-        const bool tail = (totv[k] & 255u) != 0u;
-        if (units == 1u)
-            rec[vb] = static_cast<uint32_t>(k + 1u) | (tail ? kRecTail : 0u);
-        else if (units != 0u)
-        {
-            rec[vb] = static_cast<uint32_t>(k + 1u);
-            if (tail)
-                rec[vb + units - 1u] = kRecTail;
-        }
-    }
-    if (gid == 0)
-        vbase[nsel] = static_cast<uint32_t>(hdr->vtotal);
-}
-
 // Full blocks: every wave owns a run of kRunDefault consecutive VIRTUAL units
 // with the k_dec256v32w pipeline, as k_sel_dec does.  Lane t resolves the
 // selection k of virtual unit first + t from the head records inside the run
 // and one search over vbase for the run's first unit, gathers sel[k],
 // ufirst[k] and list_unit[sel[k]] and loads the offsets of its SOURCE unit.
-// Delta-1: the start of source unit su is one more gather -- start0[list] for
-// the list's first unit, else unit_last[su - 1] (su - 1 is a unit of the same
-// list: in range whatever the table holds) -- settled with the output plane's
-// gathers before the chunks go in flight.  The output of a run is one
-// contiguous range: one buffer descriptor, stores past it dropped.
+// Delta-1: the start of source unit su is one more gather (unit_start,
+// p4_lists_dev.h), settled with the output plane's gathers before the chunks
+// go in flight.  The output of a run is one contiguous range: one buffer
+// descriptor, stores past it dropped.
 template <bool D1, uint32_t NC, int MINW>
 __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
 {
@@ -382,21 +282,18 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
     // the run's source units, for the error report only (k_sel_dec: held in a
     // register across the pipeline they cost spilled VGPRs at 7 waves)
     __shared__ uint32_t srcu[4][kRunDefault];
-    if (!un_go(A.hdr, A.out_values, A.vcap))
+    if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
     constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    uint32_t * scr = scratch[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
     const uint64_t vt = A.hdr->vtotal;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, vt);
+    const uint32_t t = R.t, wv = R.wv;
+    const uint64_t first = R.first;
     if (first >= vt)
         return; // the grid is sized by the host's cap
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, vt - first));
-    const bool valid = t < n;
+    uint32_t * slot = slots[wv];
+    uint32_t * scr = scratch[wv];
+    const bool valid = t < R.n;
     const uint64_t v = first + t;
     const uint32_t r = valid ? A.rec[v] : 0u;
     const bool full = valid && (r & kRecTail) == 0u;
@@ -417,7 +314,7 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
     const uint64_t o = full ? A.off[su] : 0ull;
     const uint64_t e = full ? A.off[su + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
-    P.init(in_base, in_end, o, e, full);
+    P.init(R.in_base, R.in_end, o, e, full);
     if (t < kRun)
         srcu[wv][t] = full ? su : 0xFFFFFFFFu;
 
@@ -430,49 +327,21 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
     if constexpr (D1)
     {
         if (full)
-            startv = inu == 0u ? (A.start0 != nullptr ? A.start0[lj] : 0u) : A.unit_last[su - 1u];
+            startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
     }
     Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
+    pipe_prime<NC>(P, C, t);
 
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((fullmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         u32x4 x;
-        const uint32_t used = decode_block256v32(slot, (ctl >> kCtlShift) & 15u, P.head(c, ctl, slot), scr, t, x);
-        if constexpr (D1)
-            apply_delta1_256(x, rl(startv, jj));
+        decode_full_unit<D1>(P, c, jj, slot, scr, rl(startv, jj), t, x, badmask);
         st16_run(ors, rl(rel, jj) + 16u * t, x);
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-
-    bool more = true;
-    for (uint32_t j = 0; more; j += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], j + q + NC - 1, t);
-                consume(C[q], j + q);
-                more = j + q + 1 < n;
-            }
-        }
-    }
-    if (A.err != nullptr && badmask != 0u)
-    {
-        // in stream numbering; the source units of a run do not ascend
-        const uint32_t m = wave_min((t < kRun && ((badmask >> t) & 1ull) != 0ull) ? srcu[wv][t] : 0xFFFFFFFFu);
-        if (t == 0)
-            atomicMin(A.err, static_cast<unsigned long long>(m));
-    }
+    });
+    report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
 }
 
 // Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
@@ -485,21 +354,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_un
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
     __shared__ uint32_t scratch[4][kListScratchU32];
-    if (!un_go(A.hdr, A.out_values, A.vcap))
+    if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
-    constexpr uint32_t kRun = kRunDefault;
-    const uint32_t t = threadIdx.x & 63u;
-    const uint32_t wv = uni(threadIdx.x >> 6);
-    uint32_t * slot = slots[wv];
-    const uint64_t in_base = reinterpret_cast<uint64_t>(A.in);
-    const uint64_t in_end = in_base + A.in_bytes;
-    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kRun;
-    if (first >= A.nsel)
+    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nsel);
+    const uint32_t t = R.t;
+    if (R.first >= A.nsel)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kRun, A.nsel - first));
-    const uint64_t k = first + t;
-    const uint64_t p0 = t < n ? A.out_ptr[k] : 0ull;
-    const uint64_t p1 = t < n ? A.out_ptr[k + 1u] : 0ull;
+    uint32_t * slot = slots[R.wv];
+    const uint64_t k = R.first + t;
+    const uint64_t p0 = t < R.n ? A.out_ptr[k] : 0ull;
+    const uint64_t p1 = t < R.n ? A.out_ptr[k + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
@@ -511,57 +375,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_un
     const uint64_t o = has ? A.off[su] : 0ull;
     const uint64_t e = has ? A.off[su + 1u] : 0ull;
     RunPlaneT<kListSlot> P;
-    P.init(in_base, in_end, o, e, has);
+    P.init(R.in_base, R.in_end, o, e, has);
     const uint64_t opos = p1 - cnt;
     uint32_t startv = 0u;
     if constexpr (D1)
     {
         if (has)
-            startv = inu == 0u ? (A.start0 != nullptr ? A.start0[lj] : 0u) : A.unit_last[su - 1u];
+            startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
     }
     uint64_t badmask = 0u;
-    auto consume = [&](const Chunk & c, uint32_t jj) {
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
         if (((hasmask >> jj) & 1ull) == 0ull)
             return;
-        const uint32_t ctl = P.stage(c, jj, slot, t);
         const uint32_t cj = rl(cnt, jj);
-        uint32_t x[4], cm;
-        const uint32_t used = decode_block_g<Fmt::H32>(slot, (ctl >> kCtlShift) & 15u, cj, scratch[wv], t, x, &cm);
-        if constexpr (D1)
-            (void)delta1_g<uint32_t>(x, cj, rl(startv, jj), t);
+        TailVals x;
+        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
         uint32_t * op = A.out + readlane_u64(opos, jj);
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
             if (t + 64u * q < cj)
-                __builtin_nontemporal_store(x[q], op + t + 64u * q);
+                __builtin_nontemporal_store(x.v[q], op + t + 64u * q);
         wave_lds_sync();
-        if (used != rl(P.len, jj))
-            badmask |= 1ull << jj;
-    };
-    Chunk C[NC];
-#pragma unroll
-    for (uint32_t q = 0; q + 1 < NC; ++q)
-        P.template issue<0>(C[q], q, t);
-    bool more = true;
-    for (uint32_t jb = 0; more; jb += NC)
-    {
-#pragma unroll
-        for (uint32_t q = 0; q < NC; ++q)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(q + NC - 1) % NC], jb + q + NC - 1, t);
-                consume(C[q], jb + q);
-                more = jb + q + 1 < n;
-            }
-        }
-    }
-    if (A.err != nullptr && badmask != 0u)
-    {
-        const uint32_t m = wave_min(((badmask >> t) & 1ull) != 0ull ? su : 0xFFFFFFFFu);
-        if (t == 0)
-            atomicMin(A.err, static_cast<unsigned long long>(m));
-    }
+    });
+    report_bad_units(A.err, badmask, su, t);
 }
 
 } // namespace tpf::dev
@@ -571,8 +409,6 @@ namespace tpf
 
 namespace
 {
-size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
-
 // Workspace of the skip-table build: header | run scan of the lists' unit
 // counts | ubase (nlists + 1) | pbase (nlists) | tail sums (nlists) | unit
 // records (nunits) | phase A (the chained decode's layout over nunits units),
@@ -587,63 +423,33 @@ struct UlWs
 
     UlWs(void * ws, uint64_t nunits, uint64_t nlists)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::ListsHdr *>(p + x);
-        x += 256u;
-        scan = RunScanWs<uint64_t>::carve(p + x, nlists);
-        x += al256(RunScanWs<uint64_t>::bytes(nlists));
-        ubase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nlists + 1u));
-        pbase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * nlists);
-        tsum = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * nlists);
-        rec = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * nunits);
-        chain = p + x;
-        x += al256(d1chain_workspace(nunits));
-        bytes = x;
+        WsCarver c(ws);
+        hdr = c.take<dev::ListsHdr>(1);
+        scan = c.scan<uint64_t>(nlists);
+        ubase = c.take<uint32_t>(nlists + 1u);
+        pbase = c.take<uint32_t>(nlists);
+        tsum = c.take<uint32_t>(nlists);
+        rec = c.take<uint32_t>(nunits);
+        chain = c.bytes<uint8_t>(d1chain_workspace(nunits));
+        bytes = c.used;
     }
 };
 
-// Workspace of the units decode: header | run scan of the selections' unit
-// counts | their value counts and that scan (u64) | vbase (nsel + 1) | records
-// of the virtual units (vcap), each 256-byte aligned.
+// Workspace of the units decode: the selection prefix (p4_lists_host.h) |
+// records of the virtual units (vcap), each 256-byte aligned.
 struct UnWs
 {
-    dev::UnHdr * hdr;
-    RunScanWs<uint64_t> scanu;
-    uint64_t *totv, *prev, *tilev;
-    uint32_t *vbase, *rec;
+    WsCarver c;
+    SelPlanWs plan;
+    uint32_t * rec;
     size_t bytes;
 
-    UnWs(void * ws, uint64_t nsel, uint64_t vcap)
+    UnWs(void * ws, uint64_t nsel, uint64_t vcap) : c(ws), plan(c, nsel)
     {
-        auto * p = static_cast<uint8_t *>(ws);
-        size_t x = 0;
-        hdr = reinterpret_cast<dev::UnHdr *>(p + x);
-        x += 256u;
-        scanu = RunScanWs<uint64_t>::carve(p + x, nsel);
-        x += al256(RunScanWs<uint64_t>::bytes(nsel));
-        totv = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * nsel);
-        prev = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * nsel);
-        tilev = reinterpret_cast<uint64_t *>(p + x);
-        x += al256(8u * RunScanWs<uint64_t>::tiles(nsel)) + 256u;
-        vbase = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * (nsel + 1u));
-        rec = reinterpret_cast<uint32_t *>(p + x);
-        x += al256(4u * vcap);
-        bytes = x;
+        rec = c.take<uint32_t>(vcap);
+        bytes = c.used;
     }
 };
-
-uint32_t flat_grid(uint64_t items, hipStream_t s)
-{
-    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
-}
 } // namespace
 
 size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists) { return UlWs(nullptr, nunits, nlists).bytes; }
@@ -705,23 +511,19 @@ hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint6
     if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || (d1 && unit_last == nullptr))
         return hipErrorInvalidValue;
     const UnWs W(ws, nsel, vcap);
-    hipError_t e = fill_u32(W.hdr, 0xFFFFFFFFu, 2, s);
+    const SelPlanWs & S = W.plan;
+    hipError_t e = fill_u32(S.hdr, 0xFFFFFFFFu, 2, s);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(dev::k_un_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, ufirst,
-                       ucount, nsel, W.scanu.tot, W.totv, W.hdr, W.rec, vcap);
+                       ucount, nsel, S.scanu.tot, S.totv, S.hdr, W.rec, vcap);
     if ((e = hipGetLastError()) != hipSuccess)
         return e;
-    if ((e = launch_run_scan_u64(W.scanu.tot, nsel, W.scanu.pre, W.scanu.tile, reinterpret_cast<uint64_t *>(&W.hdr->vtotal), s)) != hipSuccess)
-        return e;
-    if ((e = launch_run_scan_u64t(W.totv, nsel, W.prev, W.tilev, reinterpret_cast<uint64_t *>(&W.hdr->ototal), s)) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(dev::k_un_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, W.scanu.tot, W.totv,
-                       W.scanu.pre, W.scanu.tile, W.prev, W.tilev, W.hdr, W.vbase, W.rec, out_ptr, err);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_sel_heads(nsel, nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+        != hipSuccess)
         return e;
     const dev::UnArgs A{in, in_bytes, off, list_unit, start0, unit_last, sel, ufirst, ucount, nsel, out, out_values, vcap, out_ptr,
-                        W.hdr, W.rec, W.vbase, err};
+                        S.hdr, W.rec, S.vbase, err};
     // sized by the host's cap: waves past the real unit count exit
     const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
     const uint32_t tgrid = static_cast<uint32_t>((nsel + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));

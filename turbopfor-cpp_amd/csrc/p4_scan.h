@@ -84,6 +84,10 @@ struct RunScanWs
 // sum of all run totals.  T = uint64_t: byte offsets; uint32_t: sums mod 2^32.
 hipError_t launch_run_scan_u64(const uint32_t * tot, uint64_t nruns, uint64_t * pre, uint64_t * tile, uint64_t * total, hipStream_t s);
 hipError_t launch_run_scan_u32(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total, hipStream_t s);
+// the u32 scan in ONE launch while the run totals fit one tile (nruns <=
+// kScanTile), launch_run_scan_u32's two beyond: for calls that are launch-bound
+hipError_t launch_run_scan_u32_single(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total,
+                                      hipStream_t s);
 // u64 run totals (the 64-bit chained decode's unit sums, mod 2^64)
 hipError_t launch_run_scan_u64t(const uint64_t * tot, uint64_t nruns, uint64_t * pre, uint64_t * tile, uint64_t * total, hipStream_t s);
 

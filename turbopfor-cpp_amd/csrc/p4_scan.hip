@@ -90,6 +90,43 @@ __global__ __launch_bounds__(1024) void k_run_scan_tops(T * __restrict tile, uin
         *total = carry;
 }
 
+// The scan for at most ONE tile of run totals, in one launch where
+// k_run_scan_tiles and k_run_scan_tops take two: thread i sums its 16
+// consecutive entries, the 256 thread sums are scanned, pre[] = the exclusive
+// prefix, tile[0] = 0, *total = the sum.
+__global__ __launch_bounds__(256) void k_run_scan_single(const uint32_t * __restrict tot, uint32_t nruns, uint32_t * __restrict pre,
+                                                          uint32_t * __restrict tile, uint32_t * __restrict total)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t t = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t b = 16u * threadIdx.x;
+    uint32_t v[16];
+    uint32_t s = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k)
+    {
+        v[k] = s;
+        s += b + k < nruns ? tot[b + k] : 0u;
+    }
+    const uint32_t incl = wave_incl_scan(s);
+    if (t == 63u)
+        wsum[w] = incl;
+    __syncthreads();
+    uint32_t wb = 0u;
+    for (uint32_t k = 0; k < w; ++k)
+        wb += wsum[k];
+    const uint32_t ex = wb + incl - s;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k)
+        if (b + k < nruns)
+            pre[b + k] = ex + v[k];
+    if (threadIdx.x == 255u)
+    {
+        tile[0] = 0u;
+        *total = wb + incl;
+    }
+}
+
 } // namespace tpf::dev
 
 namespace tpf
@@ -125,6 +162,15 @@ hipError_t launch_run_scan_u64t(const uint64_t * tot, uint64_t nruns, uint64_t *
 hipError_t launch_run_scan_u32(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total, hipStream_t s)
 {
     return run_scan<uint32_t>(tot, nruns, pre, tile, total, s);
+}
+
+hipError_t launch_run_scan_u32_single(const uint32_t * tot, uint64_t nruns, uint32_t * pre, uint32_t * tile, uint32_t * total,
+                                      hipStream_t s)
+{
+    if (nruns > dev::kScanTile)
+        return launch_run_scan_u32(tot, nruns, pre, tile, total, s);
+    hipLaunchKernelGGL(dev::k_run_scan_single, dim3(1), dim3(256), 0, s, tot, static_cast<uint32_t>(nruns), pre, tile, total);
+    return hipGetLastError();
 }
 
 } // namespace tpf
