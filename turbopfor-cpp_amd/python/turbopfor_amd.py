@@ -844,6 +844,34 @@ def lists_gather(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, d1=F
 # ---- postings appended to a resident index (include/turbopfor_gpu.h tpf_lists_append) ----
 LISTS_APPEND_TILE = 16384  # bytes of the output one wave of the append's stitch pass moves
 
+# The caps of the lists launchers (csrc/p4_lists_host.h, p4_lists_dev.h, p4_lists_intersect.hip, p4_lists_gather.hip,
+# p4_dec_run.h), restated for the tests that have to cross them; tests/test_lists_scale_cpu.py holds them against the sources.
+LISTS_FLAT_WG_PER_CU = 8  # flat_grid: workgroups of 256 threads per CU of a grid-stride plan / heads kernel
+LISTS_MIN_W = 7           # kListsMinW: workgroups per CU of the item decodes k_ix_dec / k_ga_dec
+LISTS_IX_RUN = 4          # kIxRun: items per wave and trip of k_ix_dec
+LISTS_GA_RUN = 4          # kGaRun: items per wave and trip of k_ga_dec
+LISTS_RUN_DEFAULT = 16    # kRunDefault: units, lists, selections or items per wave of the other decodes
+
+
+def _lists_cus(device):
+    import torch
+
+    return int(torch.cuda.get_device_properties(device).multi_processor_count)
+
+
+def lists_flat_cap(device):
+    """Threads of the largest grid flat_grid launches on `device`: a plan or
+    heads kernel over more entries than this takes a second trip of its
+    grid-stride loop."""
+    return LISTS_FLAT_WG_PER_CU * 256 * _lists_cus(device)
+
+
+def lists_item_cap(device, run=LISTS_IX_RUN):
+    """Items one trip of k_ix_dec / k_ga_dec covers on `device` (4 waves per
+    workgroup, `run` items per wave): a request of more items makes every wave
+    stride."""
+    return LISTS_MIN_W * _lists_cus(device) * 4 * run
+
 
 def lists_append_units_bound(nunits, nlists_out, add_values):
     """A unit capacity that always suffices for lists_append
