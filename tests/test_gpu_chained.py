@@ -47,6 +47,52 @@ def test_chained_corrupt_offsets():
     assert int(err.item()) == 1233
 
 
+@pytest.mark.parametrize("unit,extra", [(64, 0), (70, 3)])
+def test_chained_truncated_stream(unit, extra):
+    """Only a prefix of the stream is passed, with the full offsets: cut at
+    off[64] every unit of the later 64-block runs of phase A ends past
+    in_bytes when its run is loaded (those runs stage nothing); cut at
+    off[70] + 3 a block straddles the end inside a run.  As for any offset
+    outside the stream, err is the first block whose end lies past in_bytes
+    and the blocks before it decode exactly."""
+    nb = 200
+    vals, starts = _list(nb, 5, seed=21)
+    packed_np, off_np = oracle_lib.enc256v32_batch(vals, starts=starts)
+    cut = int(off_np[unit]) + extra
+    assert int(off_np[unit]) <= cut < int(off_np[unit + 1])
+    packed = torch.from_numpy(packed_np).to(DEV)[:cut]
+    offs = torch.from_numpy(off_np.astype(np.int64)).to(DEV)
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    out = tpf.dec256v32_chained(packed, offs, nb, start0=5, err=err)
+    torch.cuda.synchronize()
+    assert int(err.item()) == unit
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32)[:unit], vals[:unit])
+
+
+def test_chained_large_roundtrip_past_one_grid():
+    """Phase A walks the runs grid-stride with at most 2 workgroups per CU,
+    each covering 4 x 64 blocks: 512 blocks per CU and pass (kDsumWgPerCu x 4
+    x kLaneRun, p4_dec256v32.hip).  Three passes and a ragged end: encode ->
+    chained decode == x."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nb = 3 * 512 * cus + 77
+    g = torch.Generator(device=DEV)
+    g.manual_seed(23)
+    gaps = torch.randint(0, 1 << 4, (nb * 256,), device=DEV, generator=g, dtype=torch.int64)
+    gaps[::4099] = 1 << 20
+    start0 = 11
+    v = (torch.cumsum(gaps + 1, 0) + start0) & 0xFFFFFFFF
+    del gaps
+    vals = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32)
+    del v
+    packed, offs = tpf.enc256v32(vals, d1=True, start0=start0)
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    out = tpf.dec256v32_chained(packed, offs, nb, start0=start0, err=err)
+    torch.cuda.synchronize()
+    assert int(err.item()) == -1
+    assert torch.equal(out.view(-1), vals)
+
+
 def test_chained_sharded_exchange():
     import tpf_shard
 

@@ -23,10 +23,11 @@ DEV = "cuda:0"
 M64 = (1 << 64) - 1
 
 
-def _list(nu, width, seed, start0):
+def _list(nu, width, seed, start0, wide_units=None):
     """Values of a chained list: per-unit gap widths 0..44 bits, 8% of gaps
     wide (exceptions), some constant-gap units; one unit of huge gaps so the
-    list wraps mod 2^64 and the running prefix crosses 2^32 many times."""
+    list wraps mod 2^64 and the running prefix crosses 2^32 many times.
+    wide_units (a slice): every gap of those units is >= 2^33."""
     rng = np.random.default_rng(seed)
     bits = rng.integers(0, 45, size=(nu, 1)).astype(np.uint64)
     gaps = rng.integers(0, 1 << 62, size=(nu, width), dtype=np.uint64) & ((np.uint64(1) << bits) - np.uint64(1))
@@ -34,6 +35,8 @@ def _list(nu, width, seed, start0):
     gaps = np.where(exc, rng.integers(0, 1 << 62, size=(nu, width), dtype=np.uint64) >> np.uint64(20), gaps)
     gaps[::9] = np.uint64(5)  # constant units
     gaps[nu // 3] = np.uint64(1) << np.uint64(61)  # the list wraps mod 2^64 here
+    if wide_units is not None:
+        gaps[wide_units] = (np.uint64(1) << np.uint64(33)) + rng.integers(0, 1 << 20, size=gaps[wide_units].shape, dtype=np.uint64)
     with np.errstate(over="ignore"):
         flat = np.cumsum(gaps.reshape(-1) + np.uint64(1), dtype=np.uint64) + np.uint64(start0)
     return flat.reshape(nu, width)
@@ -55,11 +58,16 @@ def _dev64(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(DEV)
 
 
-@pytest.mark.parametrize("fmt,nu", [("256v64", 1), ("256v64", 17), ("256v64", 701), ("128v64", 1000)])
-def test_chained64_vs_oracle_sequential(fmt, nu):
+# the last case: units 64..127 have every gap >= 2^33, so b > 32 (horizontal
+# payloads) and phase A's lane path declines all 64 lanes of one run to the
+# wave decoder, with ordinary units before and after
+@pytest.mark.parametrize("fmt,nu,wide_units", [("256v64", 1, None), ("256v64", 17, None), ("256v64", 701, None), ("128v64", 1000, None),
+                                               ("256v64", 200, slice(64, 128))],
+                         ids=["256v64-1", "256v64-17", "256v64-701", "128v64-1000", "256v64-200-declined-run"])
+def test_chained64_vs_oracle_sequential(fmt, nu, wide_units):
     width = 256 if fmt == "256v64" else 128
     start0 = (1 << 32) - 1000  # the first unit already crosses 2^32
-    vals = _list(nu, width, seed=nu, start0=start0)
+    vals = _list(nu, width, seed=nu, start0=start0, wide_units=wide_units)
     starts = np.concatenate([np.array([start0], dtype=np.uint64), vals[:-1, -1]])  # (a Python int + uint64 would go float64)
     exp_bytes = b"".join(oracle_lib.encode(fmt, vals[i], d1=True, start=int(starts[i])) for i in range(nu))
     packed, offs = tpf.enc_batch(fmt, _dev64(vals.ravel()), nu, width, d1=True, start0=start0)
@@ -144,6 +152,28 @@ def test_chained64_corrupt_offsets_reported():
     torch.cuda.synchronize()
     assert int(err.item()) == 119
     np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64)[:119], vals[:119])
+
+
+@pytest.mark.parametrize("fmt", ["256v64", "128v64"])
+@pytest.mark.parametrize("unit,extra", [(64, 0), (70, 3)])
+def test_chained64_truncated_stream(fmt, unit, extra):
+    """Only a prefix of the stream is passed, with the full offsets: cut at
+    off[64] every unit of the later 64-unit runs of phase A ends past in_bytes
+    when its run is loaded (those runs stage nothing); cut at off[70] + 3 a
+    unit straddles the end inside a run.  As for any offset outside the
+    stream, err is the first unit whose end lies past in_bytes and the units
+    before it decode exactly."""
+    nu, width = 200, (256 if fmt == "256v64" else 128)
+    vals = _list(nu, width, seed=13, start0=9)
+    packed, offs = tpf.enc_batch(fmt, _dev64(vals.ravel()), nu, width, d1=True, start0=9)
+    off_np = offs.cpu().numpy()
+    cut = int(off_np[unit]) + extra
+    assert int(off_np[unit]) <= cut < int(off_np[unit + 1])
+    err = torch.zeros(1, dtype=torch.int64, device=DEV)
+    out = tpf.dec64_chained(fmt, packed[:cut], offs, nu, start0=9, err=err)
+    torch.cuda.synchronize()
+    assert int(err.item()) == unit
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64)[:unit], vals[:unit])
 
 
 def test_chained64_large_roundtrip():

@@ -11,6 +11,7 @@
 
 #include "../../include/turbopfor_gpu.h"
 #include "p4_lists.h"
+#include "tpf_fmt.h"
 #include "tpf_kernels.h"
 
 #include <algorithm>
@@ -263,8 +264,7 @@ int tpf_p4d1enc256v32_batch(const uint32_t * d_in, uint64_t nblocks, const uint3
 extern "C++" {
 namespace tpf
 {
-// (fmt, n) pairs the batch entry points accept (also checked by the host
-// streams before they cut a batch into shards)
+// the format facts of tpf_fmt.h
 bool fmt_ok(int fmt, unsigned n)
 {
     switch (fmt)
@@ -284,11 +284,9 @@ bool fmt_ok(int fmt, unsigned n)
             return false;
     }
 }
-} // namespace tpf
-}
-using tpf::fmt_ok;
+bool wide_fmt(int fmt) { return fmt == TPF_FMT_64 || fmt == TPF_FMT_128V64 || fmt == TPF_FMT_256V64; }
 
-static unsigned unit_values(int fmt, unsigned n)
+unsigned unit_values(int fmt, unsigned n)
 {
     switch (fmt)
     {
@@ -302,11 +300,14 @@ static unsigned unit_values(int fmt, unsigned n)
             return n;
     }
 }
+} // namespace tpf
+}
+using tpf::fmt_ok;
+using tpf::unit_values;
 
 uint64_t tpf_enc_bound(int fmt, uint64_t nblocks, unsigned n)
 {
-    const bool wide = fmt == TPF_FMT_64 || fmt == TPF_FMT_128V64 || fmt == TPF_FMT_256V64;
-    return nblocks * (64u + (wide ? 18u : 8u) * unit_values(fmt, n)) + 64u;
+    return nblocks * (64u + (tpf::wide_fmt(fmt) ? 18u : 8u) * unit_values(fmt, n)) + 64u;
 }
 
 size_t tpf_enc_workspace_size(int fmt, uint64_t nblocks, unsigned n)

@@ -39,6 +39,7 @@
 #include "../../include/turbopfor.h"
 #include "../../include/turbopfor_capi.h"
 #include "../../include/turbopfor_gpu.h"
+#include "tpf_fmt.h"
 #include "tpf_kernels.h"
 #include "tpf_server.h"
 
@@ -57,22 +58,7 @@ void tpf_check(int rc, const char * what)
         throw std::runtime_error(std::string("turbopfor_amd: ") + what + ": " + tpf_last_error());
 }
 
-bool wide_fmt(int fmt) { return fmt == TPF_FMT_64 || fmt == TPF_FMT_128V64 || fmt == TPF_FMT_256V64; }
-
-unsigned unit_values(int fmt, unsigned n)
-{
-    switch (fmt)
-    {
-        case TPF_FMT_128V32:
-        case TPF_FMT_128V64:
-            return 128;
-        case TPF_FMT_256V32:
-        case TPF_FMT_256V64:
-            return 256;
-        default:
-            return n;
-    }
-}
+using tpf::unit_bytes;
 
 struct DevBuf
 {
@@ -674,8 +660,7 @@ unsigned char * enc_srv(int fmt, const void * in, unsigned n, unsigned char * ou
     Server & S = server();
     BoxLease L(S);
     tpf::ServerReqBox * b = L.req();
-    const size_t es = wide_fmt(fmt) ? 8 : 4;
-    const size_t vbytes = es * unit_values(fmt, n); // the reference also reads the full block width
+    const size_t vbytes = unit_bytes(fmt, n).vbytes; // the reference also reads the full block width
     std::memcpy(b->in, in, vbytes);
     b->op = tpf::kOpEnc;
     b->fmt = static_cast<uint32_t>(fmt);
@@ -714,8 +699,7 @@ const unsigned char * dec_srv(int fmt, const unsigned char * in, unsigned n, voi
     const tpf::ServerAnsBox * a = L.ans();
     if (a->result != size)
         throw std::runtime_error("turbopfor_amd: malformed P4 block (length check failed on the device)");
-    const size_t es = wide_fmt(fmt) ? 8 : 4;
-    std::memcpy(out, a->out, es * a->written);
+    std::memcpy(out, a->out, unit_bytes(fmt, n).es * a->written);
     return in + size;
 }
 
@@ -730,8 +714,7 @@ unsigned char * enc_one(int fmt, const void * in, unsigned n, unsigned char * ou
     if (g_mode.load(std::memory_order_relaxed) != 1)
         return enc_srv(fmt, in, n, out, d1, start);
     Ctx & c = Ctx::get();
-    const size_t es = wide_fmt(fmt) ? 8 : 4;
-    const size_t vbytes = es * unit_values(fmt, n);
+    const size_t vbytes = unit_bytes(fmt, n).vbytes;
     const uint64_t cap = tpf_enc_bound(fmt, 1, n);
     void * hv = c.h_vals.get(vbytes);
     std::memcpy(hv, in, vbytes); // the reference also reads the full block width
@@ -763,8 +746,7 @@ const unsigned char * dec_one(int fmt, const unsigned char * in, unsigned n, voi
     const uint64_t size = tpf_block_size(fmt, in, uint64_t(1) << 20, n, &written);
     if (size == 0)
         throw std::runtime_error("turbopfor_amd: malformed P4 block header");
-    const size_t es = wide_fmt(fmt) ? 8 : 4;
-    const size_t vbytes = es * unit_values(fmt, n);
+    const auto [es, vbytes] = unit_bytes(fmt, n);
     auto * hin = static_cast<uint8_t *>(c.h_in.get(size));
     std::memcpy(hin, in, size);
     auto * hoff = static_cast<uint64_t *>(c.h_off.get(4 * sizeof(uint64_t)));

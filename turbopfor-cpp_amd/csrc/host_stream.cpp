@@ -32,6 +32,7 @@
 #include "../../include/turbopfor_capi.h"
 #include "../../include/turbopfor_gpu.h"
 #include "shard_exec.h"
+#include "tpf_fmt.h"
 #include "tpf_kernels.h"
 
 namespace tpf
@@ -61,22 +62,7 @@ bool sdma_down()
     return !(e && std::strcmp(e, "kernel") == 0);
 }
 
-bool wide_fmt(int fmt) { return fmt == TPF_FMT_64 || fmt == TPF_FMT_128V64 || fmt == TPF_FMT_256V64; }
-
-unsigned unit_values(int fmt, unsigned n)
-{
-    switch (fmt)
-    {
-        case TPF_FMT_128V32:
-        case TPF_FMT_128V64:
-            return 128;
-        case TPF_FMT_256V32:
-        case TPF_FMT_256V64:
-            return 256;
-        default:
-            return n;
-    }
-}
+using tpf::unit_bytes;
 
 struct Err : std::runtime_error
 {
@@ -417,8 +403,7 @@ int host_dec_impl(int fmt, const uint8_t * h_in, uint64_t in_bytes, const uint64
                 throw Err(TPF_EINVAL, "tpf_host_dec: h_off decreases at block " + std::to_string(-bad - 1));
         }
         need_device();
-        const size_t es = wide_fmt(fmt) ? 8 : 4;
-        const size_t uv = unit_values(fmt, n);
+        const size_t es = unit_bytes(fmt, n).es, uv = tpf::unit_values(fmt, n);
         const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nblocks, chunk_value_bytes() / (es * uv)));
         // only this call's byte range of h_in (a shard of tpf_host_dec_multi reads no more)
         const Reach r_in = reach(h_in + h_off[0], h_off[nblocks] - h_off[0]);
@@ -562,8 +547,7 @@ int tpf_host_dec_multi(const int * devs, int ndev, int fmt, const uint8_t * h_in
         for (int d = 0; d < ndev; ++d)
             if (devs[d] < 0 || devs[d] >= cnt)
                 throw Err(TPF_EINVAL, "tpf_host_dec_multi: device " + std::to_string(devs[d]) + " is not visible");
-        const size_t es = wide_fmt(fmt) ? 8 : 4;
-        const size_t uv = unit_values(fmt, n);
+        const size_t es = unit_bytes(fmt, n).es, uv = tpf::unit_values(fmt, n);
         // shard cuts: equal shares of the stream's bytes (block granularity)
         std::vector<uint64_t> cut(static_cast<size_t>(ndev) + 1, nblocks);
         cut[0] = 0;
@@ -619,8 +603,7 @@ int tpf_host_enc(int fmt, const void * h_vals, uint64_t nblocks, unsigned n, int
         if (nblocks == 0)
             return TPF_OK;
         need_device();
-        const size_t es = wide_fmt(fmt) ? 8 : 4;
-        const size_t uv = unit_values(fmt, n);
+        const size_t es = unit_bytes(fmt, n).es, uv = tpf::unit_values(fmt, n);
         const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nblocks, chunk_value_bytes() / (es * uv)));
         const Reach r_vals = reach(h_vals, nblocks * uv * es), r_out = reach(h_out, out_cap);
         const Reach r_st = (d1 && h_starts) ? reach(h_starts, nblocks * es) : Reach{};
@@ -748,8 +731,7 @@ int tpf_host_enc_multi(const int * devs, int ndev, int fmt, const void * h_vals,
         for (int d = 0; d < ndev; ++d)
             if (devs[d] < 0 || devs[d] >= cnt)
                 throw Err(TPF_EINVAL, "tpf_host_enc_multi: device " + std::to_string(devs[d]) + " is not visible");
-        const size_t es = wide_fmt(fmt) ? 8 : 4;
-        const size_t uv = unit_values(fmt, n);
+        const size_t es = unit_bytes(fmt, n).es, uv = tpf::unit_values(fmt, n);
         const auto * vals = static_cast<const uint8_t *>(h_vals);
         std::vector<uint64_t> cut(static_cast<size_t>(ndev) + 1);
         for (int d = 0; d <= ndev; ++d)

@@ -201,29 +201,11 @@ __global__ __launch_bounds__(256, MINW) void k_dec256v32w(const DecArgs A)
             badmask |= 1ull << jj;
     };
 
-    // NC register chunks rotate (loop unrolled by NC, no copies): while block
-    // j is decoded, blocks j+1 .. j+NC-1 are in flight.
-    auto run_pass = [&]() {
-        Chunk C[NC];
-#pragma unroll
-        for (uint32_t u = 0; u + 1 < NC; ++u)
-            issue(C[u], u);
-        bool more = true;
-        for (uint32_t j = 0; more; j += NC)
-        {
-#pragma unroll
-            for (uint32_t u = 0; u < NC; ++u)
-            {
-                if (more)
-                {
-                    issue(C[(u + NC - 1) % NC], j + u + NC - 1);
-                    consume(C[u], j + u);
-                    more = j + u + 1 < ng;
-                }
-            }
-        }
-    };
-    run_pass();
+    // NC register chunks rotate (ring_drain, p4_dec_run.h: no copies): while
+    // block j is decoded, blocks j+1 .. j+NC-1 are in flight.
+    Chunk C[NC];
+    ring_prime<NC>(C, issue);
+    ring_drain<NC>(C, ng, issue, consume);
     if (A.err != nullptr && t == 0 && badmask != 0u)
         atomicMin(A.err, static_cast<unsigned long long>(first + stride * __builtin_ctzll(badmask)));
 }

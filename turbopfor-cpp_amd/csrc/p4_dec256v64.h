@@ -255,23 +255,8 @@ __global__ __launch_bounds__(256, 6) void k_dec128v64w(const Dec64Args A)
     };
 
     Chunk C[NC];
-#pragma unroll
-    for (uint32_t u = 0; u + 1 < NC; ++u)
-        P.template issue<0>(C[u], u, t);
-    bool more = true;
-    for (uint32_t j = 0; more; j += NC)
-    {
-#pragma unroll
-        for (uint32_t u = 0; u < NC; ++u)
-        {
-            if (more)
-            {
-                P.template issue<0>(C[(u + NC - 1) % NC], j + u + NC - 1, t);
-                consume(C[u], j + u);
-                more = j + u + 1 < n;
-            }
-        }
-    }
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, n, t, consume);
     if constexpr (SM == Start64::Probe)
         return;
     const uint64_t badmask = usedv.bad(P.len, valid);

@@ -1,7 +1,8 @@
-// p4_dec_run.h -- per-wave run machinery shared by the 256v32 decode kernels
-// (p4_dec256v32.hip, p4_d1chain.hip) and the lists kernels (p4_lists*.hip): the
-// run's control plane held in vector lanes, the register-chunk loads, the LDS
-// staging of one block and (the lists kernels) the rotating pipeline loop.
+// p4_dec_run.h -- per-wave run machinery shared by the decode kernels
+// (p4_dec256v32.h, p4_dec256v64.h, p4_generic.hip) and the lists kernels
+// (p4_lists*.hip): the run's control plane held in vector lanes, the
+// register-chunk loads, the LDS staging of one block, and the rotating
+// issue / consume loop, which the encoders' walks use too.
 #pragma once
 
 #include "p4_block32.h"

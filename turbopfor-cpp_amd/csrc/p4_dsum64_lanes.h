@@ -27,65 +27,6 @@
 namespace tpf::dev
 {
 
-// Base payload sum of one lane's 128v32-layout block (4 streams of b dwords)
-// at LDS byte pay, 64-bit exact; P pre levels, L levels (as base_sum_lanes).
-template <uint32_t P, uint32_t L, uint32_t LIM>
-__device__ __forceinline__ uint64_t base_sum4_lanes(const uint32_t * w, uint32_t pay, uint32_t b, bool on, uint32_t bmax,
-                                                    const uint32_t * row)
-{
-    const uint32_t meta = row[15];
-    const uint32_t c32 = meta & 0xFFu, pre = (meta >> 12) & 15u, T = meta >> 16;
-    uint32_t PA[P > 0 ? P : 1], PB[P > 0 ? P : 1], QA[L > 0 ? L : 1], QB[L > 0 ? L : 1], W[L > 0 ? L : 1];
-#pragma unroll
-    for (uint32_t l = 0; l < L; ++l)
-    {
-        const uint32_t a = row[l], bb = row[5 + l];
-        W[l] = row[10 + l];
-        if (l < P)
-        {
-            PA[l] = l < pre ? a : 0xFFFFFFFFu;
-            PB[l] = l < pre ? bb : 0u;
-        }
-        QA[l] = l >= pre ? a : 0xFFFFFFFFu;
-        QB[l] = l >= pre ? bb : 0u;
-    }
-    const uint32_t m = pay & 3u;
-    uint32_t q = min(pay, LIM) >> 2;
-    uint32_t phi = 0u;
-    uint64_t bs = 0ull;
-    for (uint32_t k = 0; k < bmax; ++k)
-    {
-        const uint32_t s = phi ? b - phi : 0u;
-        uint32_t d[5];
-#pragma unroll
-        for (uint32_t l = 0; l < 5u; ++l)
-            d[l] = w[q + l];
-        // the 4 folded dwords summed in 64 bits (base_sum_lanes, round 5)
-        uint64_t firsts = 0ull, acc = 0ull;
-#pragma unroll
-        for (uint32_t l = 0; l < 4u; ++l)
-        {
-            const uint32_t x = __builtin_amdgcn_alignbyte(d[l + 1], d[l], m);
-            firsts += __builtin_amdgcn_ubfe(x, 0u, s);
-            uint32_t z = x >> s;
-#pragma unroll
-            for (uint32_t lv = 0; lv < P; ++lv)
-                z = (z & PA[lv]) + ((z >> W[lv]) & PB[lv]);
-            acc += z;
-        }
-        uint32_t lo = __builtin_amdgcn_ubfe(static_cast<uint32_t>(acc), 0u, T);
-        const uint64_t hi = acc >> T;
-#pragma unroll
-        for (uint32_t lv = (P < 1u ? P : 1u); lv < L; ++lv)
-            lo = (lo & QA[lv]) + ((lo >> W[lv]) & QB[lv]);
-        bs += on && k < b ? (firsts << phi) + lo + hi : 0ull;
-        q = min(q + 4u, LIM / 4u);
-        phi += c32;
-        phi = phi >= b ? phi - b : phi;
-    }
-    return bs;
-}
-
 // vbGet64Inline's value (p4_scalar_internal.h:638-670) from its marker m and
 // the 8 bytes after it, D
 __device__ __forceinline__ uint64_t vb64_value(uint32_t m, uint64_t D)
@@ -220,56 +161,12 @@ __device__ __forceinline__ uint32_t dsum_block128v64_lanes(const uint32_t * w, u
     // positions: strictly increasing (the reference ORs repeated ones) and < 128
     if (__ballot(ok && is_vb) != 0ull)
     {
-        // 16 positions per step from 5 aligned dwords (round 6, as the 32-bit
-        // phase A; one LDS byte read per position before)
-        const bool on = ok && is_vb;
-        const uint32_t kmax = uni(wave_max_u32(on ? xn : 0u));
-        const uint32_t m = vend & 3u;
-        uint32_t prev = 0u;
-        bool inc = true;
-        for (uint32_t k0 = 0; k0 < kmax; k0 += 16u)
-        {
-            const uint32_t q = min(vend + k0, LIM) >> 2;
-            uint32_t d[5];
-#pragma unroll
-            for (uint32_t u = 0; u < 5u; ++u)
-                d[u] = w[q + u];
-#pragma unroll
-            for (uint32_t u = 0; u < 16u; ++u)
-            {
-                const uint32_t a = __builtin_amdgcn_alignbyte(d[(u >> 2) + 1], d[u >> 2], m);
-                const uint32_t pos = __builtin_amdgcn_ubfe(a, 8u * (u & 3u), 8u) + 1u; // 1..256: the first compares against 0
-                inc = inc && (!(on && k0 + u < xn) || (pos > prev && pos <= 128u));
-                prev = pos;
-            }
-        }
+        const bool inc = positions_increase<LIM>(w, vend, xn, ok && is_vb, 128u); // by the whole wave: not behind a per-lane &&
         ok = ok && (!is_vb || inc);
         len = is_vb ? vend + xn - p : len;
     }
-
-    // base payload (b <= 32: four streams of b dwords); the fold depth per wave as in dsum_lanes
-    const bool on = ok && !is_const && b != 0u;
-    const uint32_t bmax = uni(wave_max_u32(on ? b : 0u));
-    const uint32_t lmax = uni(wave_max_u32(on ? sum_levels(tab, b) : 0u));
-    const uint32_t pmax = uni(wave_max_u32(on ? sum_pre(tab, b) : 0u));
-    uint64_t bs = 0ull;
-    if (bmax != 0u)
-    {
-        const uint32_t * row = tab + (on ? b : 0u) * kSumTabRow;
-        const uint32_t key = pmax * 8u + lmax;
-        if (key == 1u * 8u + 3u)
-            bs = base_sum4_lanes<1, 3, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 1u * 8u + 2u)
-            bs = base_sum4_lanes<1, 2, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 1u * 8u + 1u)
-            bs = base_sum4_lanes<1, 1, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 2u * 8u + 4u)
-            bs = base_sum4_lanes<2, 4, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 3u * 8u + 5u)
-            bs = base_sum4_lanes<3, 5, LIM>(w, pay, b, on, bmax, row);
-        else
-            bs = base_sum4_lanes<0, 0, LIM>(w, pay, b, on, bmax, row); // every lane b = 32
-    }
+    // base payload (b <= 32: four streams of b dwords, summed exactly in 64 bits)
+    const uint64_t bs = base_sum_wave<4, uint64_t, LIM>(w, pay, b, ok && !is_const && b != 0u, tab);
     sum = is_const ? 128ull * (cv + 1ull) : bs + 128ull + shl64(exsum, b);
     return len;
 }

@@ -125,12 +125,17 @@ __device__ __forceinline__ uint32_t vb_val32(uint32_t by, uint32_t d)
     return by < 0x9Cu ? by : by < 0xDCu ? v2 : by < 0xFCu ? v3 : by == 0xFCu ? (d & 0xFFFFFFu) : d;
 }
 
-// Base payload sum of one lane's block (see dsum_lanes): P pre levels per
-// dword, L levels in all (per-lane rows whose own counts are smaller hold
-// no-op masks for the extra levels).
-template <uint32_t P, uint32_t L, uint32_t LIM>
-__device__ __forceinline__ uint32_t base_sum_lanes(const uint32_t * w, uint32_t pay, uint32_t b, bool on, uint32_t bmax,
-                                                   const uint32_t * row)
+#ifndef TPF_DSUM_ABLATE
+#define TPF_DSUM_ABLATE 0 // measurement builds only (p4_dsum_walk.h): 1 base payload, 2 compressed vbyte, 4 raw vbyte, 8 positions
+#endif
+
+// Base payload sum of one lane's block (see dsum_lanes): NS interleaved
+// streams of b dwords each (8: 256v32; 4: the 128v32 layout of a 128v64 block
+// with b <= 32, p4_dsum64_lanes.h), summed in Acc (u32 mod 2^32, or u64
+// exact); P pre levels per dword, L levels in all (per-lane rows whose own
+// counts are smaller hold no-op masks for the extra levels).
+template <uint32_t NS, class Acc, uint32_t P, uint32_t L, uint32_t LIM>
+__device__ __forceinline__ Acc base_sum_lanes(const uint32_t * w, uint32_t pay, uint32_t b, bool on, uint32_t bmax, const uint32_t * row)
 {
     const uint32_t meta = row[15];
     const uint32_t c32 = meta & 0xFFu, pre = (meta >> 12) & 15u, T = meta >> 16;
@@ -150,24 +155,27 @@ __device__ __forceinline__ uint32_t base_sum_lanes(const uint32_t * w, uint32_t 
     }
     const uint32_t m = pay & 3u;
     uint32_t q = min(pay, LIM) >> 2;
-    uint32_t phi = 0u, bs = 0u;
-    uint32_t d[9];
+    uint32_t phi = 0u;
+    Acc bs = 0;
+    // the 8-stream loop carries d[0] = d[NS] across stream words (the same
+    // dword: q advances by NS and a valid lane's q is never clamped); the
+    // 4-stream loop reloads it (the carry cost k_dsum128v64_lanes a VGPR)
+    constexpr bool kCarry = NS == 8u;
+    uint32_t d[NS + 1u];
     d[0] = w[q];
     for (uint32_t k = 0; k < bmax; ++k)
     {
         const uint32_t s = phi ? b - phi : 0u;
-        // d[0] is the previous word's d[8] (the same dword: q advances by 8
-        // and a valid lane's q is never clamped)
 #pragma unroll
-        for (uint32_t l = 1; l < 9u; ++l)
+        for (uint32_t l = kCarry ? 1u : 0u; l <= NS; ++l)
             d[l] = w[q + l];
-        // the 8 folded dwords summed in 64 bits (one add with carry each,
+        // the NS folded dwords summed in 64 bits (one add with carry each,
         // round 5): slots below T cannot carry into T, so the low T bits
         // are their sums and the bits from T up the cut top slots' sum
-        uint32_t firsts = 0u;
+        Acc firsts = 0;
         uint64_t acc = 0ull;
 #pragma unroll
-        for (uint32_t l = 0; l < 8u; ++l)
+        for (uint32_t l = 0; l < NS; ++l)
         {
             const uint32_t x = __builtin_amdgcn_alignbyte(d[l + 1], d[l], m);
             firsts += __builtin_amdgcn_ubfe(x, 0u, s);
@@ -178,7 +186,7 @@ __device__ __forceinline__ uint32_t base_sum_lanes(const uint32_t * w, uint32_t 
             acc += z;
         }
         uint32_t lo = __builtin_amdgcn_ubfe(static_cast<uint32_t>(acc), 0u, T);
-        const uint32_t hi = static_cast<uint32_t>(acc >> T);
+        const Acc hi = static_cast<Acc>(acc >> T);
         // levels pre..L-1 of each lane: a lane narrower in pre than the
         // wave's P (e.g. b = 6 beside b = 2) still needs levels pre..P-1
         // here, so the loop starts at the smallest pre any b < 32 has (1);
@@ -186,18 +194,82 @@ __device__ __forceinline__ uint32_t base_sum_lanes(const uint32_t * w, uint32_t 
 #pragma unroll
         for (uint32_t lv = (P < 1u ? P : 1u); lv < L; ++lv)
             lo = (lo & QA[lv]) + ((lo >> W[lv]) & QB[lv]);
-        bs += on && k < b ? (firsts << phi) + lo + hi : 0u;
-        q = min(q + 8u, LIM / 4u);
-        d[0] = d[8];
+        bs += on && k < b ? (firsts << phi) + lo + hi : Acc(0);
+        q = min(q + NS, LIM / 4u);
+        if constexpr (kCarry)
+            d[0] = d[NS];
         phi += c32;
         phi = phi >= b ? phi - b : phi;
     }
     return bs;
 }
 
-#ifndef TPF_DSUM_ABLATE
-#define TPF_DSUM_ABLATE 0 // measurement builds only (p4_dec256v32.hip): 1 base payload, 2 compressed vbyte, 4 raw vbyte, 8 positions
-#endif
+// The base payload sum of every lane of a wave (on: the lane has a payload of
+// width b at LDS byte pay).  Per stream word k the NS dwords share phi = 32k
+// mod b.  Per dword: the first piece (x & mask(s)) << phi is summed raw; the
+// rest z = x >> s (whole fields from bit 0) is folded `pre` SWAR levels, its
+// top slot split off; the dwords' folded parts are added, and the sum folded
+// the remaining levels once per stream word (the fold is linear while no slot
+// overflows: see build_sum_row).  The level counts are template parameters: a
+// wave's (max pre, max levels) is always that of its narrowest block, so six
+// instantiations cover every wave, and the fold runs exactly its levels (with
+// run-time counts the compiler if-converts every possible level into selects:
+// 243 VALU per stream word instead of ~110 at b = 6).
+template <uint32_t NS, class Acc, uint32_t LIM>
+__device__ __forceinline__ Acc base_sum_wave(const uint32_t * w, uint32_t pay, uint32_t b, bool on, const uint32_t * tab)
+{
+    const uint32_t bmax = uni(wave_max_u32(on ? b : 0u));
+    const uint32_t lmax = uni(wave_max_u32(on ? sum_levels(tab, b) : 0u));
+    const uint32_t pmax = uni(wave_max_u32(on ? sum_pre(tab, b) : 0u));
+    if ((TPF_DSUM_ABLATE & 1) != 0 || bmax == 0u)
+        return 0;
+    const uint32_t * row = tab + (on ? b : 0u) * kSumTabRow;
+    const uint32_t key = pmax * 8u + lmax;
+    if (key == 1u * 8u + 3u)
+        return base_sum_lanes<NS, Acc, 1, 3, LIM>(w, pay, b, on, bmax, row);
+    if (key == 1u * 8u + 2u)
+        return base_sum_lanes<NS, Acc, 1, 2, LIM>(w, pay, b, on, bmax, row);
+    if (key == 1u * 8u + 1u)
+        return base_sum_lanes<NS, Acc, 1, 1, LIM>(w, pay, b, on, bmax, row);
+    if (key == 2u * 8u + 4u)
+        return base_sum_lanes<NS, Acc, 2, 4, LIM>(w, pay, b, on, bmax, row);
+    if (key == 3u * 8u + 5u)
+        return base_sum_lanes<NS, Acc, 3, 5, LIM>(w, pay, b, on, bmax, row);
+    return base_sum_lanes<NS, Acc, 0, 0, LIM>(w, pay, b, on, bmax, row); // every lane b = 32
+}
+
+// The xn position bytes at LDS byte vend strictly increase and stay below
+// `limit` (the block's value count).  The sum is exact only then: the
+// reference ORs exceptions that share a position (patch loop
+// p4d1dec256v32_scalar.cpp:260); the wave decoder takes those blocks.
+// 16 positions per step from 5 aligned dwords.  Every lane of the wave calls
+// it (on: the lane has positions to check): the trip count is a wave maximum.
+template <uint32_t LIM>
+__device__ __forceinline__ bool positions_increase(const uint32_t * w, uint32_t vend, uint32_t xn, bool on, uint32_t limit)
+{
+    const uint32_t kmax = uni(wave_max_u32(on ? xn : 0u));
+    const uint32_t m = vend & 3u;
+    uint32_t prev = 0u;
+    bool inc = true;
+    for (uint32_t k0 = 0; k0 < kmax; k0 += 16u)
+    {
+        const uint32_t q = min(vend + k0, LIM) >> 2;
+        uint32_t d[5];
+#pragma unroll
+        for (uint32_t u = 0; u < 5u; ++u)
+            d[u] = w[q + u];
+#pragma unroll
+        for (uint32_t u = 0; u < 16u; ++u)
+        {
+            const uint32_t a = __builtin_amdgcn_alignbyte(d[(u >> 2) + 1], d[u >> 2], m);
+            const uint32_t pos = __builtin_amdgcn_ubfe(a, 8u * (u & 3u), 8u) + 1u; // 1..256: the first compares against 0
+            inc = inc && (!(on && k0 + u < xn) || (pos > prev && pos <= limit));
+            prev = pos;
+        }
+    }
+    return inc;
+}
+
 template <uint32_t LIM>
 __device__ __forceinline__ bool dsum_lanes(const uint32_t * w, uint32_t p, uint32_t len, bool act, const uint32_t * tab, uint32_t & sum)
 {
@@ -391,69 +463,12 @@ __device__ __forceinline__ bool dsum_lanes(const uint32_t * w, uint32_t p, uint3
         ok = ok && (!comp || fast || (inb && vend + xn - p == len));
     }
     pay = is_vb ? p + 2u : pay;
-    // positions must strictly increase for the sum to be exact: the
-    // reference ORs exceptions that share a position (patch loop
-    // p4d1dec256v32_scalar.cpp:260); the wave decoder takes those blocks.
-    // 16 positions per step from 5 aligned dwords.
     if ((TPF_DSUM_ABLATE & 8) == 0 && __ballot(ok && is_vb) != 0ull)
     {
-        const bool on = ok && is_vb;
-        const uint32_t kmax = uni(wave_max_u32(on ? xn : 0u));
-        const uint32_t m = vend & 3u;
-        uint32_t prev = 0u;
-        bool inc = true;
-        for (uint32_t k0 = 0; k0 < kmax; k0 += 16u)
-        {
-            const uint32_t q = min(vend + k0, LIM) >> 2;
-            uint32_t d[5];
-#pragma unroll
-            for (uint32_t u = 0; u < 5u; ++u)
-                d[u] = w[q + u];
-#pragma unroll
-            for (uint32_t u = 0; u < 16u; ++u)
-            {
-                const uint32_t a = __builtin_amdgcn_alignbyte(d[(u >> 2) + 1], d[u >> 2], m);
-                const uint32_t pos = __builtin_amdgcn_ubfe(a, 8u * (u & 3u), 8u) + 1u; // 1..256: the first compares against 0
-                inc = inc && (!(on && k0 + u < xn) || pos > prev);
-                prev = pos;
-            }
-        }
+        const bool inc = positions_increase<LIM>(w, vend, xn, ok && is_vb, 256u); // by the whole wave: not behind a per-lane &&
         ok = ok && (!is_vb || inc);
     }
-
-    // base payload: per stream word k the 8 dwords share phi = 32k mod b.
-    // Per dword: the first piece (x & mask(s)) << phi is summed raw; the rest
-    // z = x >> s (whole fields from bit 0) is folded `pre` SWAR levels, its
-    // top slot split off; the 8 dwords' folded parts are added, and the sum
-    // folded the remaining levels once per stream word (the fold is linear
-    // while no slot overflows: see build_sum_row).  The level counts are
-    // template parameters: a wave's (max pre, max levels) is always that of
-    // its narrowest block, so six instantiations cover every wave, and the
-    // fold runs exactly its levels (with run-time counts the compiler
-    // if-converts every possible level into selects: 243 VALU per stream
-    // word instead of ~110 at b = 6).
-    const bool on = ok && b != 0u;
-    const uint32_t bmax = uni(wave_max_u32(on ? b : 0u));
-    const uint32_t lmax = uni(wave_max_u32(on ? sum_levels(tab, b) : 0u));
-    const uint32_t pmax = uni(wave_max_u32(on ? sum_pre(tab, b) : 0u));
-    uint32_t bs = 0u;
-    if ((TPF_DSUM_ABLATE & 1) == 0 && bmax != 0u)
-    {
-        const uint32_t * row = tab + (on ? b : 0u) * kSumTabRow;
-        const uint32_t key = pmax * 8u + lmax;
-        if (key == 1u * 8u + 3u)
-            bs = base_sum_lanes<1, 3, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 1u * 8u + 2u)
-            bs = base_sum_lanes<1, 2, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 1u * 8u + 1u)
-            bs = base_sum_lanes<1, 1, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 2u * 8u + 4u)
-            bs = base_sum_lanes<2, 4, LIM>(w, pay, b, on, bmax, row);
-        else if (key == 3u * 8u + 5u)
-            bs = base_sum_lanes<3, 5, LIM>(w, pay, b, on, bmax, row);
-        else
-            bs = base_sum_lanes<0, 0, LIM>(w, pay, b, on, bmax, row); // every lane b = 32
-    }
+    const uint32_t bs = base_sum_wave<8, uint32_t, LIM>(w, pay, b, ok && b != 0u, tab);
     sum = is_const ? 256u * (cv + 1u) : bs + 256u + shl32(exsum, b);
     return ok;
 }

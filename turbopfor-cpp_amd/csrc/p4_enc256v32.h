@@ -28,6 +28,7 @@
 // data-movement ceiling (profiles/archive/r1/r1_v4_enc_probe.txt).
 #pragma once
 
+#include "p4_dec_run.h"
 #include "p4_scan.h"
 
 #include "p4_enc32.h"
@@ -125,23 +126,9 @@ struct EncRunT
     __device__ __forceinline__ void walk(uint32_t t, Body && body) const
     {
         u32x4 C[NC];
-#pragma unroll
-        for (uint32_t u = 0; u + 1 < NC; ++u)
-            C[u] = load(u, t);
-        bool more = true;
-        for (uint32_t j = 0; more; j += NC)
-        {
-#pragma unroll
-            for (uint32_t u = 0; u < NC; ++u)
-            {
-                if (more)
-                {
-                    C[(u + NC - 1) % NC] = load(j + u + NC - 1, t);
-                    body(C[u], j + u);
-                    more = j + u + 1 < n;
-                }
-            }
-        }
+        auto ld = [&](u32x4 & c, uint32_t jj) { c = load(jj, t); };
+        ring_prime<NC>(C, ld);
+        ring_drain<NC>(C, n, ld, body);
     }
 };
 
@@ -299,12 +286,10 @@ __global__ __launch_bounds__(256) void k_enc256v32_write(const uint32_t * __rest
 namespace tpf::enc256
 {
 
-inline size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
-
 inline uint64_t enc_runs(uint64_t nblocks, uint32_t run = dev::kEncRun) { return (nblocks + run - 1u) / run; }
 
 // two-pass encoder workspace: plan words + the run scan (p4_scan.h)
-inline size_t twopass_workspace(uint64_t nblocks) { return al256(nblocks * 4u) + RunScanWs<uint64_t>::bytes(enc_runs(nblocks)); }
+inline size_t twopass_workspace(uint64_t nblocks) { return PlanWs<uint32_t>::bytes(nblocks, enc_runs(nblocks)); }
 
 // plan -> run scan -> write.  PP / PW: PROBE of the plan / write kernel (0 =
 // production; the probes are instantiated only by the measurement library,
@@ -313,11 +298,12 @@ template <int PP, int PW>
 hipError_t launch_twopass(const uint32_t * in, uint64_t nblocks, const uint32_t * starts, uint32_t start0, bool d1, uint8_t * out,
                           uint64_t out_cap, uint64_t * off, void * ws, hipStream_t stream)
 {
-    uint32_t * plan = static_cast<uint32_t *>(ws);
     constexpr uint32_t RD = dev::kEncRunD1;
     const uint32_t run = d1 ? RD : dev::kEncRun;
     const uint64_t nruns = enc_runs(nblocks, run); // <= enc_runs(nblocks): fits the workspace
-    const RunScanWs<uint64_t> rs = RunScanWs<uint64_t>::carve(static_cast<uint8_t *>(ws) + al256(nblocks * 4u), nruns);
+    const PlanWs<uint32_t> w = PlanWs<uint32_t>::carve(ws, nblocks, nruns);
+    uint32_t * plan = w.plan;
+    const RunScanWs<uint64_t> & rs = w.scan;
     const uint64_t per_wg = 4ull * run;
     const uint32_t grid = static_cast<uint32_t>((nblocks + per_wg - 1) / per_wg);
     if constexpr (PP != 0)

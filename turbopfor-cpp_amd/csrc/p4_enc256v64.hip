@@ -297,6 +297,9 @@ struct EncRun64
     template <class Body>
     __device__ __forceinline__ void walk(uint32_t t, Body && body) const
     {
+        // the ring written out (ring_drain, p4_dec_run.h, is this loop): through
+        // the shared template the delta-1 write kernels allocate 4-5 fewer
+        // VGPRs and change occupancy, which this kernel's tuning did not see
         Chunk64 C[kEnc64NC];
 #pragma unroll
         for (uint32_t u = 0; u + 1 < kEnc64NC; ++u)
@@ -436,10 +439,7 @@ __global__ __launch_bounds__(256) void k_enc128v64_write(const uint64_t * __rest
 namespace tpf
 {
 
-size_t enc128v64_workspace(uint64_t nunits)
-{
-    return ((nunits * 8u + 255u) & ~size_t(255)) + RunScanWs<uint64_t>::bytes((nunits + dev::kEnc64Run - 1u) / dev::kEnc64Run);
-}
+size_t enc128v64_workspace(uint64_t nunits) { return PlanWs<uint64_t>::bytes(nunits, (nunits + dev::kEnc64Run - 1u) / dev::kEnc64Run); }
 
 namespace
 {
@@ -449,10 +449,10 @@ hipError_t enc64_launch(const uint64_t * in, uint64_t nunits, const uint64_t * s
 {
     if (ws_bytes < enc128v64_workspace(nunits))
         return hipErrorInvalidValue;
-    auto * plan = static_cast<uint64_t *>(ws);
-    const size_t plan_bytes = (nunits * 8u + 255u) & ~size_t(255);
     const uint64_t nruns = (nunits + dev::kEnc64Run - 1u) / dev::kEnc64Run;
-    const RunScanWs<uint64_t> rs = RunScanWs<uint64_t>::carve(static_cast<uint8_t *>(ws) + plan_bytes, nruns);
+    const PlanWs<uint64_t> w = PlanWs<uint64_t>::carve(ws, nunits, nruns);
+    uint64_t * plan = w.plan;
+    const RunScanWs<uint64_t> & rs = w.scan;
     const uint64_t per_wg = 4ull * dev::kEnc64Run;
     const uint32_t grid = static_cast<uint32_t>((nunits + per_wg - 1) / per_wg);
     hipLaunchKernelGGL((dev::k_enc128v64_plan<NB, D1>), dim3(grid), dim3(256), 0, s, in, nunits, starts, start0, off, plan, rs.tot);

@@ -95,6 +95,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_de
         if (used != rl(P.len, jj))
             badmask |= 1ull << jj;
     };
+    // the ring written out (pipe_drain, p4_dec_run.h, is this loop): through
+    // the shared template the delta-1 forms of the 32-bit formats allocate 4-7
+    // more VGPRs and lose a wave per SIMD
     Chunk C[NC];
 #pragma unroll
     for (uint32_t u = 0; u + 1 < NC; ++u)
@@ -511,26 +514,12 @@ __global__ __launch_bounds__(256) TPF_SGPR_ATTR void k_enc_gr(const typename Fmt
             img[i] = 0u;
         wave_lds_sync();
     }
-    // NC units rotate in registers (loop unrolled by NC, no copies of
+    // NC units rotate in registers (ring_drain, p4_dec_run.h: no copies of
     // in-flight loads): while unit j is encoded, j+1 .. j+NC-1 are in flight.
     Unit4<T> C[NC];
-#pragma unroll
-    for (uint32_t u = 0; u + 1 < NC; ++u)
-        R.load(u, t, C[u].v);
-    bool more = true;
-    for (uint32_t j = 0; more; j += NC)
-    {
-#pragma unroll
-        for (uint32_t u = 0; u < NC; ++u)
-        {
-            if (more)
-            {
-                R.load(j + u + NC - 1, t, C[(u + NC - 1) % NC].v);
-                body(C[u], j + u);
-                more = j + u + 1 < R.nr;
-            }
-        }
-    }
+    auto ld = [&](Unit4<T> & c, uint32_t jj) { R.load(jj, t, c.v); };
+    ring_prime<NC>(C, ld);
+    ring_drain<NC>(C, R.nr, ld, body);
     if constexpr (!WRITE)
     {
         if (t < R.nr)
@@ -549,8 +538,6 @@ namespace tpf
 
 namespace
 {
-
-size_t plan_bytes(uint64_t nblocks) { return (nblocks * 4u + 255u) & ~size_t(255); }
 
 template <dev::Fmt F>
 hipError_t dec_fmt(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nblocks, uint32_t n, void * out,
@@ -601,8 +588,9 @@ hipError_t enc_fmt_d(const void * in, uint64_t nblocks, uint32_t n, const void *
     const uint64_t nruns = (nblocks + dev::kGRun - 1u) / dev::kGRun;
     if (ws_bytes < generic_workspace(nblocks))
         return hipErrorInvalidValue;
-    uint32_t * plan = static_cast<uint32_t *>(ws);
-    const RunScanWs<uint64_t> rs = RunScanWs<uint64_t>::carve(static_cast<uint8_t *>(ws) + plan_bytes(nblocks), nruns);
+    const PlanWs<uint32_t> w = PlanWs<uint32_t>::carve(ws, nblocks, nruns);
+    uint32_t * plan = w.plan;
+    const RunScanWs<uint64_t> & rs = w.scan;
     hipLaunchKernelGGL((dev::k_enc_gr<F, D1, false>), dim3(g), dim3(256), 0, s, ip, nblocks, n, sp, static_cast<T>(start0), off, plan,
                        rs.tot, nullptr, nullptr, out, out_cap);
     hipError_t e = hipGetLastError();
@@ -627,7 +615,7 @@ hipError_t enc_fmt(const void * in, uint64_t nblocks, uint32_t n, bool d1, const
 } // namespace
 
 // plan words (one per unit, 256-B aligned) + the run scan
-size_t generic_workspace(uint64_t nblocks) { return plan_bytes(nblocks) + RunScanWs<uint64_t>::bytes((nblocks + dev::kGRun - 1u) / dev::kGRun); }
+size_t generic_workspace(uint64_t nblocks) { return PlanWs<uint32_t>::bytes(nblocks, (nblocks + dev::kGRun - 1u) / dev::kGRun); }
 
 hipError_t launch_dec_generic(int fmt, const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nblocks, uint32_t n,
                               void * out, const void * starts, unsigned long long * err, hipStream_t s)

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tpf_ws.h"
+
 namespace tpf::dev
 {
 
@@ -76,9 +78,6 @@ constexpr uint32_t kItemNone = 0xFFFFFFFFu; // unit word / list word: the reques
 
 namespace tpf
 {
-
-template <class T>
-struct RunScanWs; // p4_scan.h
 
 size_t lists_workspace(uint64_t nunits, uint64_t nlists);
 // The passes the decode and the encode (p4_lists_enc.hip) share: header reset,

@@ -1,8 +1,7 @@
 // p4_lists_host.h -- host helpers shared by the launch functions of the lists
-// entry points (p4_lists*.hip): the 256-byte alignment of workspace arrays, the
-// carver every workspace struct lays its arrays out with, the grid of a
-// grid-stride kernel, and the workspace prefix the selective decode and the
-// units decode share (internal).
+// entry points (p4_lists*.hip): the grid of a grid-stride kernel and the
+// workspace prefix the selective decode and the units decode share (internal;
+// the workspace carver is tpf_ws.h).
 #pragma once
 
 #include "p4_lists.h"
@@ -12,41 +11,11 @@
 namespace tpf
 {
 
-inline size_t al256(size_t x) { return (x + 255u) & ~size_t(255); }
-
 // workgroups of 256 threads for a grid-stride kernel over `items`
 inline uint32_t flat_grid(uint64_t items, hipStream_t s)
 {
     return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255u) / 256u, grid_cap(s, 8))));
 }
-
-// Hands out consecutive arrays of a workspace, each starting 256-byte aligned;
-// `used` is the size of everything handed out so far (a null base: sizes only).
-struct WsCarver
-{
-    uint8_t * base;
-    size_t used = 0;
-
-    explicit WsCarver(void * ws) : base(static_cast<uint8_t *>(ws)) {}
-
-    template <class T>
-    T * bytes(size_t nbytes)
-    {
-        T * r = reinterpret_cast<T *>(base + used);
-        used += al256(nbytes);
-        return r;
-    }
-    template <class T>
-    T * take(uint64_t count)
-    {
-        return bytes<T>(sizeof(T) * count);
-    }
-    template <class T>
-    RunScanWs<T> scan(uint64_t nruns)
-    {
-        return RunScanWs<T>::carve(bytes<uint8_t>(RunScanWs<T>::bytes(nruns)), nruns);
-    }
-};
 
 // Workspace prefix of a decode over a selection: header | run scan of the
 // selections' unit counts | their value counts and that scan (u64) | vbase

@@ -14,6 +14,7 @@
 #pragma once
 
 #include "tpf_device.h"
+#include "tpf_ws.h"
 
 namespace tpf::dev
 {
@@ -54,27 +55,64 @@ __device__ __forceinline__ void run_offsets(uint64_t * __restrict off, uint64_t 
 namespace tpf
 {
 
-// Workspace of the run scan: run totals (u32), in-tile prefixes and tile
+// Workspace of the run scan: run totals (Tot), in-tile prefixes and tile
 // totals (T), each 256-byte aligned.
-template <class T>
+template <class T, class Tot>
 struct RunScanWs
 {
-    uint32_t * tot = nullptr;
+    Tot * tot = nullptr;
     T * pre = nullptr;
     T * tile = nullptr;
 
-    static size_t al(size_t x) { return (x + 255u) & ~size_t(255); }
     static uint64_t tiles(uint64_t nruns) { return (nruns + dev::kScanTile - 1u) / dev::kScanTile; }
-    static size_t bytes(uint64_t nruns) { return al(4u * nruns) + al(sizeof(T) * nruns) + al(sizeof(T) * tiles(nruns)) + 256u; }
+    static size_t bytes(uint64_t nruns) { return al256(sizeof(Tot) * nruns) + al256(sizeof(T) * nruns) + al256(sizeof(T) * tiles(nruns)) + 256u; }
     static RunScanWs carve(void * ws, uint64_t nruns)
     {
+        WsCarver c(ws);
         RunScanWs w;
-        auto * p = static_cast<uint8_t *>(ws);
-        w.tot = reinterpret_cast<uint32_t *>(p);
-        p += al(4u * nruns);
-        w.pre = reinterpret_cast<T *>(p);
-        p += al(sizeof(T) * nruns);
-        w.tile = reinterpret_cast<T *>(p);
+        w.tot = c.take<Tot>(nruns);
+        w.pre = c.take<T>(nruns);
+        w.tile = c.take<T>(tiles(nruns));
+        return w;
+    }
+};
+
+// Workspace of a two-pass encoder: one plan word (P) per unit, then the run
+// scan of the runs' byte totals.
+template <class P>
+struct PlanWs
+{
+    P * plan;
+    RunScanWs<uint64_t> scan;
+
+    static size_t bytes(uint64_t nunits, uint64_t nruns) { return al256(sizeof(P) * nunits) + RunScanWs<uint64_t>::bytes(nruns); }
+    static PlanWs carve(void * ws, uint64_t nunits, uint64_t nruns)
+    {
+        WsCarver c(ws);
+        PlanWs w;
+        w.plan = c.take<P>(nunits);
+        w.scan = c.scan<uint64_t>(nruns);
+        return w;
+    }
+};
+
+// Workspace of a chained delta-1 decode: the unit sums of phase A (T), then
+// the run scan over T totals of phase B's 16-unit runs.
+template <class T>
+struct ChainWs
+{
+    static constexpr uint32_t kRun = 16; // == dev::kRunDefault == dev::kRun64
+    T * sums;
+    RunScanWs<T, T> scan;
+
+    static uint64_t runs(uint64_t nunits) { return (nunits + kRun - 1u) / kRun; }
+    static size_t bytes(uint64_t nunits) { return al256(sizeof(T) * nunits) + RunScanWs<T, T>::bytes(runs(nunits)); }
+    static ChainWs carve(const void * ws, uint64_t nunits)
+    {
+        WsCarver c(ws);
+        ChainWs w;
+        w.sums = c.take<T>(nunits);
+        w.scan = c.scan<T, T>(runs(nunits));
         return w;
     }
 };

@@ -56,9 +56,6 @@ struct ServerAns;
 struct ServerCtl;
 hipError_t launch_block_server(ServerReq * d_req, ServerAns * d_ans, ServerCtl * d_ctl, hipStream_t s);
 
-// (fmt, n) accepted by the batch entry points (capi.cpp)
-bool fmt_ok(int fmt, unsigned n);
-
 size_t generic_workspace(uint64_t nblocks);
 hipError_t launch_dec_generic(int fmt, const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nblocks, uint32_t n,
                               void * out, const void * starts, unsigned long long * err, hipStream_t s);
