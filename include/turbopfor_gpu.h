@@ -22,7 +22,32 @@
  *     never followed;
  *   - decoded values are nblocks * 256 contiguous integers.
  * No device-side slack is required: all device reads are bounds-checked
- * against in_bytes.
+ * against in_bytes, and no byte at or after d_in + in_bytes can change a
+ * result (d_in may start at any byte address).
+ *
+ * WORKSPACE CONTRACT (every codec entry point below that takes d_ws; the lists
+ * entry points state the same for themselves):
+ *   - d_ws holds at least the bytes the matching *_workspace_size export
+ *     returns for the same counts and is at least 8-byte aligned; a smaller
+ *     ws_bytes is TPF_EINVAL ("workspace too small") and nothing is enqueued,
+ *     not even the initialisation of d_err.  The exports are multiples of 256
+ *     and non-decreasing in their count, so one buffer sized for the largest
+ *     batch serves every smaller one;
+ *   - nothing outside [d_ws, d_ws + size export) is read or written;
+ *   - its contents on entry are irrelevant: no call relies on what it, or any
+ *     other call, left there;
+ *   - the next call on the same stream may reuse it at once, without a
+ *     synchronisation in between -- but for a chain_decode, which reads what
+ *     the chain_sums before it wrote (below);
+ *   - a call may be captured into a hipGraph and replayed on a workspace
+ *     that was overwritten in between.
+ * OUTPUT CONTRACT: a decoder writes exactly the values its section names
+ * (nblocks * 256, nunits * width, nblocks * n for the horizontal formats, n
+ * for an n-variant stream) and nothing before or after them; d_off is count +
+ * 1 entries, d_err one u64, d_total one element.  Every encoder writes
+ * d_off[0..count] and the stream's d_off[count] bytes of d_out: the bytes of
+ * d_out between the stream's end and out_cap are left untouched, on every
+ * route (tests/test_gpu_codec_workspace.py holds all of this).
  *
  * Return value: TPF_OK (0) or a negative TPF_E* code; tpf_last_error()
  * returns a thread-local message for the last failure.
@@ -69,7 +94,11 @@ int tpf_p4d1dec256v32_batch(const uint8_t *d_in, uint64_t in_bytes, const uint64
  * decodes with start(i) = base + prefix(i-1).  tpf_p4d1dec256v32_chained = A+B
  * with base = start0.  For a list sharded over GPUs, each rank runs A, the
  * ranks exchange their totals (d_total, one u32 each) and each runs B with
- * base = start0 + the totals of all earlier shards (mod 2^32). */
+ * base = start0 + the totals of all earlier shards (mod 2^32).
+ * d_ws: tpf_p4d1dec256v32_chain_workspace_size(nblocks) bytes under the
+ * WORKSPACE CONTRACT above.  chain_decode only reads it: it may run any number
+ * of times, with any base, against one chain_sums, and leaves every byte as
+ * phase A wrote it. */
 size_t tpf_p4d1dec256v32_chain_workspace_size(uint64_t nblocks);
 int tpf_p4d1dec256v32_chained(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nblocks,
                               uint32_t *d_out, uint32_t start0, void *d_ws, size_t ws_bytes, uint64_t *d_err,
@@ -90,7 +119,8 @@ int tpf_p4d1dec256v32_chain_decode(const uint8_t *d_in, uint64_t in_bytes, const
  * workspace; phase B (chain_decode) decodes with start(i) = base + the totals
  * before i.  tpf_d1dec64_chained = A + B with base = start0; for a sharded list
  * exchange the d_total of each shard (one u64) as for 256v32.  d_out: nunits *
- * 128 * (1 or 2) u64. */
+ * 128 * (1 or 2) u64.  d_ws: tpf_d1dec64_chain_workspace_size(nunits) bytes
+ * under the WORKSPACE CONTRACT above; chain_decode only reads it. */
 size_t tpf_d1dec64_chain_workspace_size(uint64_t nunits);
 int tpf_d1dec64_chained(int fmt, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
                         uint64_t *d_out, uint64_t start0, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
@@ -113,7 +143,9 @@ int tpf_p4d1dec128v64_chained(const uint8_t *d_in, uint64_t in_bytes, const uint
  * sizes are only known on the device, so a smaller out_cap is rejected with
  * TPF_EINVAL instead of risking a silently cut-off block)
  * and their byte offsets into d_off[0..nblocks] (d_off[nblocks] = total).
- * d_ws: device workspace of tpf_p4enc256v32_workspace_size(nblocks) bytes.
+ * d_ws: device workspace of tpf_p4enc256v32_workspace_size(nblocks) bytes
+ * under the WORKSPACE CONTRACT above.  Bytes of d_out past d_off[nblocks] are
+ * left untouched.
  * D1: d_starts[i] is the value preceding block i; with d_starts == NULL the
  * blocks are one chained posting list: block 0 starts from start0 and block
  * i>0 from the last input value of block i-1. */
@@ -151,7 +183,12 @@ int tpf_p4d1enc256v32_batch(const uint32_t *d_in, uint64_t nblocks, const uint32
  * tpf_dec_batch reports through d_err (first such block index) any block whose
  * parse disagrees with its offsets; for TPF_FMT_32 (the windowed decoder) also
  * any block whose offsets span more than 2,544 bytes or run past in_bytes --
- * a p4Enc32 block of n <= 256 values is at most about 1 KB. */
+ * a p4Enc32 block of n <= 256 values is at most about 1 KB.
+ * tpf_enc_batch's d_ws: tpf_enc_workspace_size(fmt, nblocks, n) bytes under
+ * the WORKSPACE CONTRACT above, on each of its three routes (256v32 with n ==
+ * 256; 128v64 with n == 128 and 256v64; every other (fmt, n)); bytes of d_out
+ * past d_off[nblocks] are left untouched.  tpf_dec_batch takes no workspace
+ * and writes nblocks * stride values (stride as above), nothing after them. */
 uint64_t tpf_enc_bound(int fmt, uint64_t nblocks, unsigned n);
 size_t tpf_enc_workspace_size(int fmt, uint64_t nblocks, unsigned n);
 int tpf_dec_batch(int fmt, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nblocks, unsigned n,
@@ -168,7 +205,11 @@ int tpf_enc_batch(int fmt, const void *d_vals, uint64_t nblocks, unsigned n, int
  * before it, the first = start0).  d_off receives nunits + 1 byte offsets
  * (nunits = n/256 + (n%256 != 0)); d_off[nunits] is the stream's length.
  * Decode takes the same offsets (tpf_scan_offsets of the parts, or the
- * encoder's) and writes exactly n values. */
+ * encoder's) and writes exactly n values.
+ * d_ws: tpf_p4nenc256v32_workspace_size(n) / tpf_p4ndec256v32_workspace_size(n)
+ * bytes under the WORKSPACE CONTRACT above (both keep u64 words in its first
+ * 256 bytes, hence the 8-byte alignment); the encoder leaves the bytes of
+ * d_out past d_off[nunits] untouched. */
 uint64_t tpf_p4nenc256v32_bound(uint64_t n);
 size_t tpf_p4nenc256v32_workspace_size(uint64_t n);
 int tpf_p4nenc256v32(const uint32_t *d_in, uint64_t n, int d1, uint32_t start0, uint8_t *d_out, uint64_t out_cap,

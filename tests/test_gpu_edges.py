@@ -64,9 +64,10 @@ def test_stream_over_4gib_roundtrip():
 
 def test_hipgraph_capture_replay():
     """The batched entry points allocate nothing and only launch on the given
-    stream, so a decode + chained-D1 decode + encode sequence can be captured
-    into one hipGraph (torch.cuda.CUDAGraph on ROCm) and replayed with new
-    inputs written into the same buffers."""
+    stream, so the plain 256v32 encode followed by the plain 256v32 decode of
+    its output can be captured into one hipGraph (torch.cuda.CUDAGraph on ROCm)
+    and replayed with new inputs written into the same buffers.  (The chained
+    and n-variant calls are captured in tests/test_gpu_codec_workspace.py.)"""
     nb = 3000
     g = torch.Generator(device=DEV)
     g.manual_seed(5)

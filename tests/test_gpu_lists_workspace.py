@@ -21,6 +21,7 @@ import pytest
 import lists_index as li
 import lists_ref as ref
 import lists_scale as sc
+from guarded import Workspace
 from lists_index import CLEAN, DEV, SENT, SENT64, Index
 
 torch = pytest.importorskip("torch")
@@ -28,32 +29,7 @@ tpf = pytest.importorskip("turbopfor_amd")
 
 pytestmark = pytest.mark.gpu
 SMALL = [300, 0, 612, 256, 90, 0, 256 * 17]
-GUARD = 4096
-FILL = 0xC3
 SENT8 = 0xA5
-
-
-class Workspace:
-    """A view of exactly `size` bytes, `mis` bytes past a 256-byte boundary, with at least GUARD sentinel bytes on either side."""
-
-    def __init__(self, size, mis=0):
-        self.size = size
-        self.big = torch.full((GUARD + 256 + size + GUARD,), FILL, dtype=torch.uint8, device=DEV)
-        self.s = GUARD + (mis - (self.big.data_ptr() + GUARD)) % 256
-        self.view = self.big[self.s: self.s + size]
-        assert self.view.data_ptr() % 256 == mis and self.view.numel() == size
-
-    def fill(self, what):
-        """what: a byte, or a uint8 device tensor that is repeated over the view"""
-        if isinstance(what, int):
-            self.view.fill_(what)
-        else:
-            reps = -(-self.size // what.numel())
-            self.view.copy_(what.repeat(reps)[: self.size])
-
-    def intact(self):
-        got = self.big.cpu().numpy()
-        return bool((got[: self.s] == FILL).all() and (got[self.s + self.size:] == FILL).all())
 
 
 class Small:

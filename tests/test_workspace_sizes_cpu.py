@@ -83,6 +83,26 @@ def test_enc_workspace_size(lib, fmt, n):
     assert [int(lib.tpf_enc_workspace_size(FMT[fmt], c, n)) for c in COUNTS] == ENC[(fmt, n)]
 
 
+SWEEP = 70_000  # past 65,537 units: the scan over 16-unit runs has crossed one tile of 4096 run totals
+
+
+def _swept(f):
+    """A caller sizes one buffer for its largest batch and reuses it for every smaller one, at a 256-byte granule."""
+    v = [int(f(c)) for c in range(SWEEP + 1)]
+    assert all(x % 256 == 0 for x in v)
+    assert all(a <= b for a, b in zip(v, v[1:]))
+
+
+@pytest.mark.parametrize("name", sorted(ONE_COUNT))
+def test_workspace_size_of_one_count_is_monotonic_in_256_byte_steps(lib, name):
+    _swept(getattr(lib, name))
+
+
+@pytest.mark.parametrize("fmt,n", sorted(ENC))
+def test_enc_workspace_size_is_monotonic_in_256_byte_steps(lib, fmt, n):
+    _swept(lambda c: lib.tpf_enc_workspace_size(FMT[fmt], c, n))
+
+
 def test_lists_decode_workspace_size(lib):
     got = [[int(lib.tpf_p4ndec256v32_lists_workspace_size(u, l)) for l in COUNTS] for u in COUNTS]
     assert got == LISTS

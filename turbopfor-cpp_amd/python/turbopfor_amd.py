@@ -118,6 +118,9 @@ def lib():
             L.tpf_d1dec64_chained.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_d1dec64_chain_sums.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]
             L.tpf_d1dec64_chain_decode.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]
+            for name in ("tpf_p4d1dec256v64_chained", "tpf_p4d1dec128v64_chained"):
+                getattr(L, name).argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp]
+                getattr(L, name).restype = ctypes.c_int
             for name in ("tpf_d1dec64_chained", "tpf_d1dec64_chain_sums", "tpf_d1dec64_chain_decode"):
                 getattr(L, name).restype = ctypes.c_int
         # the many-lists decode: absent from older builds loaded through TPF_LIB
@@ -319,31 +322,38 @@ def enc256v32_path(mode, values, out, d1=False, starts=None, start0=0):
     return offs
 
 
-def enc256v32(values, d1=False, starts=None, start0=0, out=None):
+def enc256v32(values, d1=False, starts=None, start0=0, out=None, offs=None, ws=None):
     """Encode values (int32/uint32-bit CUDA tensor, nblocks*256 elements) as
     256v32 P4 blocks.  Returns (packed uint8 tensor sized to the encoded
     total, offsets int64 tensor [nblocks+1]).  d1 selects p4D1Enc256v32:
     starts (int32 [nblocks]) gives each block's preceding value, or with
-    starts=None the blocks form one chained list starting after start0."""
+    starts=None the blocks form one chained list starting after start0.
+    out / offs / ws: optional preallocated buffers (out's numel() is the
+    capacity, ws's the workspace size); with out and offs both given the call
+    stays asynchronous and returns out untrimmed."""
     import torch
 
     assert values.is_cuda and values.dtype in (torch.int32,) and values.numel() % 256 == 0
     values = values.contiguous()
     nb = values.numel() // 256
     L = lib()
-    cap = int(L.tpf_p4enc256v32_bound(nb))
+    trim = out is None or offs is None
     if out is None:
-        out = torch.empty(cap, dtype=torch.uint8, device=values.device)
-    offs = torch.empty(nb + 1, dtype=torch.int64, device=values.device)
+        out = torch.empty(int(L.tpf_p4enc256v32_bound(nb)), dtype=torch.uint8, device=values.device)
+    if offs is None:
+        offs = torch.empty(nb + 1, dtype=torch.int64, device=values.device)
     ws_bytes = int(L.tpf_p4enc256v32_workspace_size(nb))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=values.device)
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=values.device)
     if d1:
         rc = L.tpf_p4d1enc256v32_batch(_ptr(values), nb, _ptr(starts), ctypes.c_uint32(start0 & 0xFFFFFFFF),
-                                       _ptr(out), out.numel(), _ptr(offs), _ptr(ws), ws_bytes, _stream(torch))
+                                       _ptr(out), out.numel(), _ptr(offs), _ptr(ws), ws.numel(), _stream(torch))
     else:
-        rc = L.tpf_p4enc256v32_batch(_ptr(values), nb, _ptr(out), out.numel(), _ptr(offs), _ptr(ws), ws_bytes,
+        rc = L.tpf_p4enc256v32_batch(_ptr(values), nb, _ptr(out), out.numel(), _ptr(offs), _ptr(ws), ws.numel(),
                                      _stream(torch))
     _check(rc)
+    if not trim:
+        return out, offs
     total = int(offs[-1].item())
     return out[:total], offs
 
@@ -405,16 +415,20 @@ class D1Chain:
     block's delta sum and its prefix (returns the shard total as a 1-element
     int32 CUDA tensor), decode(base) writes the values.  A multi-GPU list
     runs sums() on every shard, exchanges the totals, then decode() with
-    base = start0 + sum of earlier shards' totals (mod 2^32)."""
+    base = start0 + sum of earlier shards' totals (mod 2^32).  ws / total:
+    optional caller's workspace (its numel() is the size passed) and
+    1-element int32 total."""
 
-    def __init__(self, packed, offsets, nblocks):
+    def __init__(self, packed, offsets, nblocks, ws=None, total=None):
         import torch
 
         self.packed, self.offsets, self.nblocks = packed, offsets, nblocks
         L = lib()
-        self.ws_bytes = int(L.tpf_p4d1dec256v32_chain_workspace_size(nblocks))
-        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-        self.total = torch.zeros(1, dtype=torch.int32, device=packed.device)
+        ws_bytes = int(L.tpf_p4d1dec256v32_chain_workspace_size(nblocks))
+        if ws is None or ws.numel() < ws_bytes:
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+        self.ws, self.ws_bytes = ws, ws.numel()
+        self.total = torch.zeros(1, dtype=torch.int32, device=packed.device) if total is None else total
 
     def sums(self, err=None):
         import torch
@@ -437,6 +451,43 @@ class D1Chain:
         return out
 
 
+class D1Chain64:
+    """The 64-bit counterpart of D1Chain over one chained list of fmt "256v64"
+    or "128v64" units (tpf_d1dec64_chain_sums / tpf_d1dec64_chain_decode):
+    sums() returns the shard total as a 1-element int64 CUDA tensor (mod
+    2^64), decode(base) writes int64 [nunits, 256 or 128].  ws / total:
+    optional caller's workspace (its numel() is the size passed) and
+    1-element int64 total."""
+
+    def __init__(self, fmt, packed, offsets, nunits, ws=None, total=None):
+        import torch
+
+        self.fmt, self.width = FMT[fmt], _UNIT[fmt]
+        self.packed, self.offsets, self.nunits = packed, offsets, nunits
+        ws_bytes = int(lib().tpf_d1dec64_chain_workspace_size(nunits))
+        if ws is None or ws.numel() < ws_bytes:
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+        self.ws, self.ws_bytes = ws, ws.numel()
+        self.total = torch.zeros(1, dtype=torch.int64, device=packed.device) if total is None else total
+
+    def sums(self, err=None):
+        import torch
+
+        _check(lib().tpf_d1dec64_chain_sums(self.fmt, _ptr(self.packed), self.packed.numel(), _ptr(self.offsets), self.nunits,
+                                            _ptr(self.ws), self.ws_bytes, _ptr(self.total), _ptr(err), _stream(torch)))
+        return self.total
+
+    def decode(self, base, out=None, err=None):
+        import torch
+
+        if out is None:
+            out = torch.empty((self.nunits, self.width), dtype=torch.int64, device=self.packed.device)
+        _check(lib().tpf_d1dec64_chain_decode(self.fmt, _ptr(self.packed), self.packed.numel(), _ptr(self.offsets), self.nunits,
+                                              _ptr(out), ctypes.c_uint64(base & 0xFFFFFFFFFFFFFFFF), _ptr(self.ws), _ptr(err),
+                                              _stream(torch)))
+        return out
+
+
 def dec256v32_chained(packed, offsets, nblocks, start0=0, out=None, err=None, ws=None):
     """One chained list (block i starts from block i-1's last value, block 0
     from start0): tpf_p4d1dec256v32_chained (block sums + scan, then decode).
@@ -456,10 +507,12 @@ def dec256v32_chained(packed, offsets, nblocks, start0=0, out=None, err=None, ws
     return out
 
 
-def dec64_chained(fmt, packed, offsets, nunits, start0=0, out=None, err=None, ws=None):
+def dec64_chained(fmt, packed, offsets, nunits, start0=0, out=None, err=None, ws=None, named=False):
     """One chained 64-bit list of fmt "256v64" or "128v64" units (unit i
     starts from unit i-1's last value, unit 0 from start0): tpf_d1dec64_chained
-    (unit sums + scan, then decode).  Returns int64 [nunits, 256 or 128]."""
+    (unit sums + scan, then decode), or with named=True the format's own entry
+    point tpf_p4d1dec256v64_chained / tpf_p4d1dec128v64_chained.  Returns
+    int64 [nunits, 256 or 128]."""
     import torch
 
     width = _UNIT[fmt]
@@ -469,8 +522,9 @@ def dec64_chained(fmt, packed, offsets, nunits, start0=0, out=None, err=None, ws
     ws_bytes = int(L.tpf_d1dec64_chain_workspace_size(nunits))
     if ws is None or ws.numel() < ws_bytes:
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    rc = L.tpf_d1dec64_chained(FMT[fmt], _ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(out),
-                               ctypes.c_uint64(start0 & 0xFFFFFFFFFFFFFFFF), _ptr(ws), ws.numel(), _ptr(err), _stream(torch))
+    args = (_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(out), ctypes.c_uint64(start0 & 0xFFFFFFFFFFFFFFFF), _ptr(ws),
+            ws.numel(), _ptr(err), _stream(torch))
+    rc = getattr(L, f"tpf_p4d1dec{fmt}_chained")(*args) if named else L.tpf_d1dec64_chained(FMT[fmt], *args)
     _check(rc)
     return out
 
@@ -481,38 +535,49 @@ def n_units(n):
     return n // 256 + (1 if n % 256 else 0)
 
 
-def encn256v32(values, d1=False, start0=0):
+def encn256v32(values, d1=False, start0=0, out=None, offs=None, ws=None):
     """Encode any number of int32 values as the stream the reference produces
     by chaining p4Enc256v32 over the full 256-blocks and p4Enc32 over the
     remainder (p4D1* with d1, one list starting after start0).  Returns
-    (packed uint8 tensor, offsets int64 [n_units(n) + 1])."""
+    (packed uint8 tensor, offsets int64 [n_units(n) + 1]).  out / offs / ws:
+    optional preallocated buffers (out's numel() is the capacity, ws's the
+    workspace size); with out and offs both given the call stays asynchronous
+    and returns out untrimmed."""
     import torch
 
     assert values.is_cuda and values.dtype == torch.int32
     values = values.contiguous().view(-1)
     n = values.numel()
     L = lib()
-    cap = int(L.tpf_p4nenc256v32_bound(n))
-    out = torch.empty(cap, dtype=torch.uint8, device=values.device)
-    offs = torch.empty(n_units(n) + 1, dtype=torch.int64, device=values.device)
+    trim = out is None or offs is None
+    if out is None:
+        out = torch.empty(int(L.tpf_p4nenc256v32_bound(n)), dtype=torch.uint8, device=values.device)
+    if offs is None:
+        offs = torch.empty(n_units(n) + 1, dtype=torch.int64, device=values.device)
     ws_bytes = int(L.tpf_p4nenc256v32_workspace_size(n))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=values.device)
-    _check(L.tpf_p4nenc256v32(_ptr(values), n, int(bool(d1)), ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), cap,
-                              _ptr(offs), _ptr(ws), ws_bytes, _stream(torch)))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=values.device)
+    _check(L.tpf_p4nenc256v32(_ptr(values), n, int(bool(d1)), ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), out.numel(),
+                              _ptr(offs), _ptr(ws), ws.numel(), _stream(torch)))
+    if not trim:
+        return out, offs
     return out[:int(offs[-1].item())], offs
 
 
-def decn256v32(packed, offsets, n, d1=False, start0=0, out=None, err=None):
-    """Decode an n-value stream of encn256v32's layout (offsets: n_units(n)+1)."""
+def decn256v32(packed, offsets, n, d1=False, start0=0, out=None, err=None, ws=None):
+    """Decode an n-value stream of encn256v32's layout (offsets: n_units(n)+1).
+    ws: optional reusable uint8 workspace tensor (its numel() is the size
+    passed)."""
     import torch
 
     if out is None:
         out = torch.empty(n, dtype=torch.int32, device=packed.device)
     L = lib()
     ws_bytes = int(L.tpf_p4ndec256v32_workspace_size(n))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=packed.device)
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=packed.device)
     _check(L.tpf_p4ndec256v32(_ptr(packed), packed.numel(), _ptr(offsets), n, int(bool(d1)),
-                              ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), _ptr(ws), ws_bytes, _ptr(err),
+                              ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), _ptr(ws), ws.numel(), _ptr(err),
                               _stream(torch)))
     return out
 
