@@ -169,9 +169,18 @@ int tpf_p4d1enc256v32_batch(const uint32_t *d_in, uint64_t nblocks, const uint32
  * A batch holds nblocks units; unit i's values are at d_vals + i*stride with
  * stride = n for the horizontal formats and the layout's full width (128 or
  * 256) for the interleaved ones (the reference packs the full width).
+ * PADDING CONTRACT (TPF_FMT_128V32 / TPF_FMT_256V32 with n below the width):
+ * without delta-1 a block the encoder leaves in plain mode (header b, no
+ * exceptions) carries the low b bits of the caller's slots n .. width-1, as
+ * the reference's p4Enc128v32 / p4Enc256v32 do; no other mode, and no length,
+ * depends on those slots.  With delta-1 they are never read: the padding
+ * bits are zero (the reference packs its uninitialised stack there,
+ * p4d1enc128v32_scalar.cpp:12) and the next unit of a chained list starts
+ * from value n-1.  Of a decoded unit the first n values are specified
+ * (tests/test_gpu_formats32.py holds all of this).
  * Values are uint32 or uint64 as the family requires.  D1 (delta-1): starts
  * per unit, or NULL = one chained list (encode: start0 then the previous
- * unit's last input; decode requires starts). */
+ * unit's last input, value n-1; decode requires starts). */
 #define TPF_FMT_32 0
 #define TPF_FMT_128V32 1
 #define TPF_FMT_256V32 2

@@ -13,7 +13,9 @@
 //
 // File format (little endian):
 //   "TPFG" u32 version(1) u32 count
-//   record: u32 flags  (bit0 = delta-1, bit1 = decode-only vector)
+//   record: u32 flags  (bit0 = delta-1, bit1 = decode-only vector, bit2 = n
+//                       below the layout width and the padding bits of enc
+//                       follow the zero convention, see gen64_short)
 //           u32 n      (values per call)
 //           u64 start  (delta-1 start)
 //           u32 esize  (4 or 8)
@@ -615,6 +617,203 @@ static void gen64h(Writer & w, uint64_t seed)
         }
 }
 
+// ------------------------------- 32-bit units with n below the layout width
+// p4D1Enc128v32 / p4D1Enc256v32 delta-encode n values into an uninitialised
+// stack array and hand it to the plain encoder (p4d1enc128v32_scalar.cpp:12),
+// which packs the layout's full width when it picks the plain mode: those
+// payload bits are whatever the stack held.  As add64_short: encoded after a
+// 0x00 fill and after a 0xA5 fill of the stack, flag 4 where the bytes differ.
+// The caller's slots past n are zero.
+static uint32_t enc32_ref(Fmt32 f, const std::vector<uint32_t> & in, unsigned n, bool d1, uint32_t start, uint8_t fill,
+                          std::vector<uint8_t> & enc)
+{
+    std::vector<uint32_t> buf(in);
+    std::fill(enc.begin(), enc.end(), 0);
+    fill_stack(fill);
+    uint8_t * e = nullptr;
+    if (f == F256V32)
+        e = d1 ? sc::p4D1Enc256v32(buf.data(), n, enc.data(), start) : sc::p4Enc256v32(buf.data(), n, enc.data());
+    else if (f == F128V32)
+        e = d1 ? sc::p4D1Enc128v32(buf.data(), n, enc.data(), start) : sc::p4Enc128v32(buf.data(), n, enc.data());
+    else
+        e = d1 ? sc::p4D1Enc32(buf.data(), n, enc.data(), start) : sc::p4Enc32(buf.data(), n, enc.data());
+    return static_cast<uint32_t>(e - enc.data());
+}
+
+static const uint8_t * dec32_ref(Fmt32 f, const uint8_t * enc, unsigned n, uint32_t * dec, bool d1, uint32_t start)
+{
+    uint8_t * e = const_cast<uint8_t *>(enc);
+    if (f == F256V32)
+        return d1 ? sc::p4D1Dec256v32(e, n, dec, start) : sc::p4Dec256v32(e, n, dec);
+    if (f == F128V32)
+        return d1 ? sc::p4D1Dec128v32(e, n, dec, start) : sc::p4Dec128v32(e, n, dec);
+    return d1 ? sc::p4D1Dec32(e, n, dec, start) : sc::p4Dec32(e, n, dec);
+}
+
+static void add32_short(Writer & w, Fmt32 f, const std::vector<uint32_t> & v, bool d1, uint32_t start)
+{
+    const unsigned n = static_cast<unsigned>(v.size());
+    std::vector<uint32_t> in(256 + 64, 0);
+    std::copy(v.begin(), v.end(), in.begin());
+    std::vector<uint8_t> e0(n * 5 + 4096), e1(n * 5 + 4096);
+    const uint32_t len0 = enc32_ref(f, in, n, d1, start, 0x00, e0);
+    const uint32_t len1 = enc32_ref(f, in, n, d1, start, 0xA5, e1);
+    if (len0 != len1)
+        die("32 short: length depends on stack contents", w.count);
+    const bool unpinned = std::memcmp(e0.data(), e1.data(), len0) != 0;
+    std::vector<uint32_t> dec(512 + 64, 0xDEADBEEFu);
+    if (dec32_ref(f, e0.data(), n, dec.data(), d1, start) != e0.data() + len0)
+        die("32 short decode end pointer", w.count);
+    if (std::memcmp(dec.data(), v.data(), n * 4u) != 0)
+        die("32 short round trip", w.count);
+    w.record((d1 ? 1u : 0u) | (unpinned ? 4u : 0u), n, start, 4u, v.data(), e0.data(), len0);
+}
+
+static void gen32_short(Writer & w, Fmt32 f, uint64_t seed)
+{
+    Rng r(seed);
+    const std::vector<unsigned> ns = f == F128V32 ? std::vector<unsigned>{1, 2, 7, 31, 32, 33, 63, 64, 65, 100, 127}
+                                                  : std::vector<unsigned>{1, 63, 64, 65, 127, 128, 129, 200, 255};
+    for (unsigned n : ns)
+    {
+        std::vector<uint32_t> v(n, 0u);
+        add32_short(w, f, v, false, 0); // all zero
+        std::fill(v.begin(), v.end(), 0x15u);
+        add32_short(w, f, v, false, 0); // constant, b = 5
+        std::fill(v.begin(), v.end(), 0xF0000001u);
+        add32_short(w, f, v, false, 0); // constant, b = 32
+        for (unsigned b : {1u, 8u, 17u, 32u})
+        {
+            const uint32_t mx = b == 32 ? 0xFFFFFFFFu : ((1u << b) - 1u);
+            for (auto & x : v)
+                x = static_cast<uint32_t>(r.range(0, mx));
+            v[r.range(0, n - 1)] |= 1u << (b - 1); // width exactly b
+            add32_short(w, f, v, false, 0);
+        }
+        // the exception mixes of gen32: fillWithExceptions, the ab_test distribution,
+        // mostly zero with a few large values, small values + moderate exceptions
+        for (unsigned pct : {5u, 25u})
+        {
+            for (auto & x : v)
+                x = (r.range(0, 99) < pct) ? 100000u : static_cast<uint32_t>(r.range(0, 255));
+            add32_short(w, f, v, false, 0);
+        }
+        for (unsigned bw : {4u, 12u, 20u})
+            for (double pct : {5.0, 25.0})
+            {
+                for (auto & x : v)
+                    x = (r.unit() * 100.0 < pct) ? static_cast<uint32_t>(r.range(1ull << bw, 0xFFFFFFFFull))
+                                                 : static_cast<uint32_t>(r.range(0, (1ull << bw) - 1));
+                add32_short(w, f, v, false, 0);
+            }
+        for (unsigned k : {1u, 3u})
+        {
+            std::fill(v.begin(), v.end(), 0u);
+            for (unsigned j = 0; j < k && j < n; ++j)
+                v[r.range(0, n - 1)] = static_cast<uint32_t>(r.range(1, 0xFFFFFFFFull));
+            add32_short(w, f, v, false, 0);
+        }
+        for (unsigned k : {4u, 12u, 30u})
+            for (uint32_t emax : {300u, 3000000u})
+            {
+                for (auto & x : v)
+                    x = static_cast<uint32_t>(r.range(0, 15));
+                for (unsigned j = 0; j < k && j < n; ++j)
+                    v[r.range(0, n - 1)] = static_cast<uint32_t>(r.range(16, emax));
+                add32_short(w, f, v, false, 0);
+            }
+        // delta-1 lists: sorted with bounded gaps, one wrapping 2^32, Zipf-ish gaps
+        for (uint32_t md : {1u, 15u, 255u, 65535u})
+        {
+            uint32_t st;
+            auto s = sortedSeq(r, n, md, st);
+            add32_short(w, f, s, true, st);
+        }
+        {
+            uint32_t st = 0xFFFFFF00u, cur = st;
+            for (auto & x : v)
+                x = (cur += static_cast<uint32_t>(r.range(1, 9)));
+            add32_short(w, f, v, true, st);
+        }
+        for (unsigned rep = 0; rep < 2; ++rep)
+        {
+            uint32_t cur = static_cast<uint32_t>(r.range(0, 1u << 20)), st = cur;
+            for (auto & x : v)
+                x = (cur += zipfGap(r));
+            add32_short(w, f, v, true, st);
+        }
+    }
+}
+
+// Compressed vbEnc32 streams with every marker length (1..5 bytes): a base of
+// width 0..8, between n/8 and n/3 exceptions whose excess over the base is
+// 1..149 (a one-byte marker), and one to three of them replaced by a value of
+// width b+9..32 (the widths rotate, so that the 2-, 3-, 4- and 5-byte forms
+// all occur).  The many short markers keep the compressed form 32 bytes under
+// the raw one.  Plain and delta-1 (the values are then the list's gaps).
+static void gen32_vbyte(Writer & w, Fmt32 f, uint64_t seed, const std::vector<unsigned> & ns, unsigned reps)
+{
+    Rng r(seed);
+    unsigned wstep = 0;
+    for (unsigned n : ns)
+        for (unsigned d1 = 0; d1 < 2; ++d1)
+            for (unsigned rep = 0; rep < reps; ++rep)
+            {
+                const unsigned b = static_cast<unsigned>(r.range(0, 8));
+                std::vector<uint32_t> v(n);
+                for (auto & x : v)
+                    x = b ? static_cast<uint32_t>(r.range(0, (1u << b) - 1u)) : 0u;
+                const unsigned xn = static_cast<unsigned>(r.range((n + 7) / 8, n / 3));
+                std::vector<unsigned> pos(n);
+                for (unsigned i = 0; i < n; ++i)
+                    pos[i] = i;
+                for (unsigned i = 0; i < xn; ++i)
+                    std::swap(pos[i], pos[i + r.range(0, n - 1 - i)]);
+                for (unsigned i = 0; i < xn; ++i)
+                    v[pos[i]] |= static_cast<uint32_t>(r.range(1, 149)) << b;
+                const unsigned big = static_cast<unsigned>(r.range(1, 3));
+                for (unsigned i = 0; i < big; ++i)
+                {
+                    const unsigned span = 32u - (b + 9u) + 1u;
+                    const unsigned wd = b + 9u + (wstep * 5u) % span;
+                    ++wstep;
+                    v[pos[i]] = (1u << (wd - 1)) | static_cast<uint32_t>(r.range(0, (1ull << (wd - 1)) - 1ull));
+                }
+                uint32_t st = 0;
+                if (d1)
+                {
+                    uint32_t cur = st = static_cast<uint32_t>(r.next());
+                    for (auto & x : v)
+                        x = (cur += x + 1u);
+                }
+                add32_short(w, f, v, d1 != 0, st);
+            }
+}
+
+// decode-only: header 0x80 | b with bx == 0 (p4dec128v32_scalar.cpp,
+// p4dec32.cpp), which the encoder never emits
+static void gen32_bx0(Writer & w, Fmt32 f, uint64_t seed, const std::vector<unsigned> & ns)
+{
+    Rng r(seed);
+    for (unsigned n : ns)
+        for (unsigned b : {8u, 32u})
+        {
+            const unsigned bb = f == F256V32 ? 32u * b : f == F128V32 ? 16u * b : (n * b + 7u) / 8u;
+            std::vector<uint8_t> enc(2 + bb + 64, 0);
+            enc[0] = static_cast<uint8_t>(0x80u | b);
+            enc[1] = 0;
+            for (unsigned i = 0; i < bb; ++i)
+                enc[2 + i] = static_cast<uint8_t>(r.next());
+            std::vector<uint32_t> dec(512 + 64, 0);
+            if (dec32_ref(f, enc.data(), n, dec.data(), false, 0) != enc.data() + 2 + bb)
+                die("32 decode-only end pointer", w.count);
+            w.record(2u, n, 0, 4u, dec.data(), enc.data(), 2 + bb);
+            if (dec32_ref(f, enc.data(), n, dec.data(), true, 0xFFFFFF00u) != enc.data() + 2 + bb)
+                die("32 decode-only D1 end pointer", w.count);
+            w.record(3u, n, 0xFFFFFF00u, 4u, dec.data(), enc.data(), 2 + bb);
+        }
+}
+
 // Hand-made decode-only vectors: valid streams the encoder never emits.
 static void genDecodeOnly(Writer & w)
 {
@@ -667,6 +866,26 @@ int main(int argc, char ** argv)
         Writer w;
         gen64h(w, 0x64);
         w.save(dir + "/g64.bin");
+    }
+    {
+        Writer w;
+        gen32_short(w, F128V32, 0x128033);
+        gen32_vbyte(w, F128V32, 0x128034, {128u, 100u}, 16u);
+        gen32_bx0(w, F128V32, 0x128035, {128u, 100u, 7u});
+        w.save(dir + "/g128v32s.bin");
+    }
+    {
+        Writer w;
+        gen32_short(w, F256V32, 0x256033);
+        gen32_vbyte(w, F256V32, 0x256034, {256u, 200u}, 16u);
+        gen32_bx0(w, F256V32, 0x256035, {200u, 65u});
+        w.save(dir + "/g256v32s.bin");
+    }
+    {
+        Writer w;
+        gen32_vbyte(w, FH32, 0x33, {127u, 256u, 100u, 200u}, 16u);
+        gen32_bx0(w, FH32, 0x34, {127u, 256u, 100u});
+        w.save(dir + "/g32vb.bin");
     }
     return 0;
 }

@@ -540,9 +540,14 @@ uint8_t *orc_p4enc32(const uint32_t *in, unsigned n, uint8_t *out) { return p4en
 
 /* p4D1Enc256v32 (p4d1enc256v32_scalar.cpp:7-15), p4D1Enc128v32, p4D1Enc32:
  * deltaEnc1 into a temporary, then the plain encoder.  For the vertical
- * layouts the temporary holds only n deltas; the tail up to the block size is
- * taken from the caller's input like the reference's stack buffer would not
- * be -- callers use n equal to the block size. */
+ * layouts with n below the block size the temporary holds n deltas and
+ * zeros past them: the caller's slots past n are not read.  The reference
+ * leaves that tail of its stack array uninitialised
+ * (p4d1enc128v32_scalar.cpp:12), and its plain-mode blocks pack it (their low
+ * b bits); tests/golden/g128v32s.bin and g256v32s.bin pin every other mode
+ * byte for byte at n = 1..255 and mark those plain-mode records with flag 4
+ * (same length, zero convention).  Without delta-1 the plain-mode block
+ * carries the caller's slots past n, here as in the reference, and is pinned. */
 static uint8_t *p4d1enc32_generic(const uint32_t *in, unsigned n, uint8_t *out, uint32_t start, int lay)
 {
     if (n == 0u) return out;

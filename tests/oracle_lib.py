@@ -96,11 +96,15 @@ _FMT = {
 }
 
 
-def encode(fmt, values, d1=False, start=0):
+def encode(fmt, values, d1=False, start=0, pad=None):
+    """pad: what the caller's slots past n hold, up to the layout width (a
+    scalar or an array for slots n..width-1; default zeros)."""
     dt, blk = _FMT[fmt]
     n = len(values)
     buf = np.zeros(max(n, 256) + 64, dtype=dt)
     buf[:n] = values
+    if pad is not None and blk is not None and n < blk:
+        buf[n:blk] = pad
     out = np.zeros(n * 10 + 4096, dtype=np.uint8)
     L = lib()
     tp = u32p if dt == np.uint32 else u64p

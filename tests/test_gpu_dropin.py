@@ -42,7 +42,8 @@ def perblock_mode(request):
 
 
 @pytest.mark.parametrize("fname,fmt", [("g32.bin", "32"), ("g128v32.bin", "128v32"), ("g256v32.bin", "256v32"),
-                                       ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64")])
+                                       ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64"),
+                                       ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32")])
 def test_per_block_mirrors_match_golden(fname, fmt, perblock_mode):
     L = capi()
     wide = fmt in ("64", "128v64", "256v64")
@@ -50,9 +51,10 @@ def test_per_block_mirrors_match_golden(fname, fmt, perblock_mode):
     vt = ctypes.c_uint64 if wide else ctypes.c_uint32
     recs = golden_io.load(fname)
     step = max(1, len(recs) // 120)  # per-block calls are latency-bound: sample
-    # ... but keep every unit shorter than the layout width (128v64 n < 128,
-    # 256v64 n < 256: split into 128v64 blocks like the reference)
-    short = [r for r in recs if wide and r.n < tpf.unit_values(fmt, r.n)]
+    # ... but keep every unit shorter than the layout width (128v32 / 128v64
+    # n < 128, 256v32 n < 256, 256v64 n < 256: split into 128v64 blocks like
+    # the reference)
+    short = [r for r in recs if r.n < tpf.unit_values(fmt, r.n)]
     for i, r in enumerate(recs[::step] + short):
         full = tpf.unit_values(fmt, r.n)
         src = np.zeros(full + 64, dtype=dt)

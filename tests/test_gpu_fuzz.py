@@ -80,7 +80,7 @@ def test_fuzz_256v32_plain_d1_chained(seed):
 
 
 @pytest.mark.parametrize("fmt,n", [("32", 127), ("128v32", 128), ("256v64", 256), ("128v64", 100), ("64", 127),
-                                    ("64", 256)])
+                                    ("64", 256), ("128v32", 100), ("256v32", 200)])
 def test_fuzz_generic_formats(fmt, n):
     rng = np.random.default_rng(7 + n)
     nb = 2000

@@ -8,7 +8,8 @@ import oracle_lib
 import p4_modes
 
 FAMILIES = [("g256v32.bin", "256v32"), ("g128v32.bin", "128v32"), ("g32.bin", "32"),
-            ("g256v64.bin", "256v64"), ("g128v64.bin", "128v64"), ("g64.bin", "64")]
+            ("g256v64.bin", "256v64"), ("g128v64.bin", "128v64"), ("g64.bin", "64"),
+            ("g256v32s.bin", "256v32"), ("g128v32s.bin", "128v32"), ("g32vb.bin", "32")]
 
 
 @pytest.mark.parametrize("fname,fmt", FAMILIES)
@@ -40,6 +41,57 @@ def test_short_64bit_units_are_pinned():
         assert len(short) >= 50
         pinned = [r for r in short if not r.padding_unpinned]
         assert len(pinned) >= len(short) // 2, (fname, len(pinned), len(short))
+
+
+def test_short_32bit_units_are_pinned():
+    """128v32 with n < 128 and 256v32 with n < 256: the reference's bytes
+    depend on its uninitialised stack (flag 4) only where p4D1Enc* hands its
+    n-delta temporary to the plain encoder and that packs the full width
+    (p4d1enc128v32_scalar.cpp:12) -- delta-1, n below the width, plain mode.
+    Everything else is byte-pinned, every vector without delta-1 included."""
+    for fname, fmt, full in (("g128v32s.bin", "128v32", 128), ("g256v32s.bin", "256v32", 256)):
+        recs = [r for r in golden_io.load(fname) if not r.decode_only]
+        for i, r in enumerate(recs):
+            if r.padding_unpinned:
+                mode = p4_modes.parse32(r.enc, 0, r.n, full)[0]
+                assert r.d1 and r.n < full and mode in ("plain", "plain32"), (fname, i, r.d1, r.n, mode)
+        short = [r for r in recs if r.n < full]
+        assert len(short) >= 200
+        assert not any(r.padding_unpinned for r in short if not r.d1)
+        pinned = [r for r in short if not r.padding_unpinned]
+        assert len(pinned) >= len(short) // 2, (fname, len(pinned), len(short))
+        assert any(r.padding_unpinned for r in short), fname  # the rule above is exercised
+
+
+def test_golden32_covers_every_mode():
+    """The 32-bit fixtures of every family (horizontal, 128v32, 256v32) reach
+    every mode of p4_modes.MODES32 -- all zero, plain, plain at width 32,
+    constant, constant at width 32, bitmap patch, the decode-only 0x80 | b
+    header with bx == 0, vbyte raw and compressed -- and their compressed
+    vbEnc32 streams carry every marker length, 1..5 bytes.  Every record
+    parses to exactly its length; the short-unit files hold every n listed."""
+    fams = {"32": ["g32.bin", "g32vb.bin"], "128v32": ["g128v32.bin", "g128v32s.bin"],
+            "256v32": ["g256v32.bin", "g256v32s.bin"]}
+    for fmt, fnames in fams.items():
+        modes, lens = set(), set()
+        for fname in fnames:
+            by_n = {}
+            for i, r in enumerate(golden_io.load(fname)):
+                m, ls, end = p4_modes.parse32(r.enc, 0, r.n, p4_modes.BASE_N32[fmt])
+                assert end == len(r.enc), (fname, i, m, end, len(r.enc))
+                assert (m == "bx0") == r.decode_only, (fname, i, m)
+                modes.add(m)
+                lens.update(ls)
+                by_n.setdefault(r.n, set()).add(m)
+            if fname == "g128v32s.bin":
+                assert set(by_n) == {1, 2, 7, 31, 32, 33, 63, 64, 65, 100, 127, 128}
+            if fname == "g256v32s.bin":
+                assert set(by_n) == {1, 63, 64, 65, 127, 128, 129, 200, 255, 256}
+            if fname.endswith("s.bin"):
+                assert any(r.d1 and r.start == 0xFFFFFF00 for r in golden_io.load(fname))  # a list that wraps 2^32
+        for m in p4_modes.MODES32:
+            assert m in modes, (fmt, m)
+        assert lens == {1, 2, 3, 4, 5}, (fmt, sorted(lens))
 
 
 def test_golden_covers_every_mode():
