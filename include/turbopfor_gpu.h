@@ -624,6 +624,97 @@ int tpf_lists_intersect(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *
                         uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
                         void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- union with a resident index ----------------------------------------------
+ * tpf_lists_union answers nq disjunctions against a delta-1 lists stream: query
+ * k is the probe values d_probe[d_probe_ptr[k] .. d_probe_ptr[k+1]), merged
+ * with list j = d_qlist[k].  It returns, per query, the sorted union of the two
+ * with where every value came from.  A k-term OR is the call chained k-1 times
+ * on the device: d_out and d_out_ptr of one call are d_probe and d_probe_ptr of
+ * the next, and the first probe is a tpf_p4ndec256v32_lists_select decode.
+ *   - The index and the probe: exactly the arguments of tpf_lists_intersect --
+ *     the stream, its offsets, d_list_ptr, d_list_unit, d_start0 (NULL means
+ *     0), the skip table d_unit_last (required); d_probe_ptr (nq + 1 entries)
+ *     non-decreasing, not necessarily from 0; nothing of d_probe outside
+ *     [d_probe_ptr[0], d_probe_ptr[nq]) is read.  Empty segments are allowed
+ *     anywhere; the same list may be the target of many queries.  d_out must
+ *     not overlap d_probe.
+ *   - Definition.  Query k has target j = d_qlist[k] of n = n_j values, probe
+ *     indices [a, b) = [d_probe_ptr[k], d_probe_ptr[k+1]), ua = d_list_unit[j]
+ *     and ub = d_list_unit[j+1].  For probe index i with value v: u is the
+ *     first unit of [ua, ub) with d_unit_last[u] >= v.  With no such unit L(i)
+ *     = n and i is a MISS.  Otherwise unit u, of cnt values, is decoded as
+ *     tpf_lists_intersect decodes it (from d_start0[j] when u == ua, else from
+ *     d_unit_last[u-1]); q is the lower bound of v over the unit's decoded
+ *     values by the intersection's branch-free search, held to cnt; L(i) =
+ *     min(256 (u - ua) + q, n); i is a HIT iff q < cnt and the value at q
+ *     equals v, else a miss.  M(i) is the number of misses among [a, i) and
+ *     M_k the number of misses of the segment.
+ *       Segment k of the output has n + M_k values at d_out[d_out_ptr[k] ..);
+ *     d_out_ptr[0] = 0: the output is dense and itself a CSR array.
+ *       Miss i goes to slot L(i) + M(i) of its segment; its d_out_pidx is i
+ *     (the index into d_probe) and its d_out_tpos is TPF_LISTS_NONE.
+ *       The list value at list position p goes to slot p + #{misses i' of the
+ *     segment with L(i') <= p}; its d_out_tpos is p and its d_out_pidx is the
+ *     probe index of the hit that equals it (the hit i with L(i) + M(i) = that
+ *     slot), or TPF_LISTS_NONE.  The list's copy of a common value is the one
+ *     kept: a hit adds no value.
+ *   - Precondition: the list ascends without wrapping mod 2^32, the table is
+ *     correct and the probe segment is strictly ascending.  Then segment k is
+ *     exactly the sorted set union of the probe segment and the list, every
+ *     slot written once, strictly ascending: a valid probe of the next call.
+ *     Lists are limited to 2^32 - 1 values (d_out_tpos is 32 bits wide).
+ *   - Outside the precondition (a list that wraps, a wrong table, an unsorted
+ *     or repeating probe) d_out_ptr is still as defined, n + M_k per segment;
+ *     the contents of the slices are unspecified; every access stays in
+ *     bounds: the table holds values, never indices.
+ *   - Output bounds: nothing is written at or past d_out + out_values (the same
+ *     for d_out_pidx and d_out_tpos), and nothing outside a query's slice.
+ *     d_out is only 4-byte aligned.  out_values = probe_values + the sum of the
+ *     targets' lengths always suffices.
+ *   - Cost: no kernel and no workspace array is sized by nlists or nunits.
+ *     Grids and the workspace -- O(nq + probe_values + out_values / 256) words
+ *     -- are sized on the host from nq, probe_values and out_values; a result
+ *     that fits holds at most out_values / 256 + nq target units, the rule of
+ *     tpf_p4ndec256v32_lists_select.  No decoded list value is staged in
+ *     global memory.  A target unit is decoded at most twice: once if probe
+ *     values land in it (the lookup), once when it is written.  Nineteen
+ *     launches for a probe of up to 262,144 values and twenty-one beyond
+ *     (each of the two run scans over the probe then takes a second launch),
+ *     one fewer without d_out_pidx: decided on the host by the arguments'
+ *     sizes, whatever the queries.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed, and the lowest code is the one reported:
+ *       < nunits        the lowest SOURCE unit, among the units decoded, whose
+ *                       parse disagrees with its offsets; the segment contents
+ *                       are unspecified but in bounds;
+ *       nunits + k      the first query k refused by any check
+ *                       tpf_lists_intersect makes on a query: nothing is
+ *                       written to d_out, d_out_ptr, d_out_pidx or d_out_tpos;
+ *       nunits + nq     the result does not fit out_values: nothing is written
+ *                       to d_out, d_out_pidx or d_out_tpos, but d_out_ptr is
+ *                       filled completely, so d_out_ptr[nq] is what to allocate.
+ *   - TPF_EINVAL (decided before any device call): with nq non-zero a null
+ *     d_in, d_off, d_list_ptr, d_list_unit, d_unit_last, d_probe_ptr, d_qlist,
+ *     d_out_ptr or d_ws; a null d_probe or d_out while probe_values or
+ *     out_values is non-zero; ws_bytes below
+ *     tpf_lists_union_workspace_size(nq, probe_values, out_values); nlists,
+ *     nunits, nq, probe_values or out_values / 256 + nq above 0x7FFFFFFF.
+ *     nq == 0 is a successful no-op that writes d_out_ptr[0] = 0 and sets d_err
+ *     to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy.
+ * d_ws: device workspace, at least 8-byte aligned. */
+#define TPF_LISTS_NONE 0xFFFFFFFFu
+size_t tpf_lists_union_workspace_size(uint64_t nq, uint64_t probe_values, uint64_t out_values);
+int tpf_lists_union(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                    const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                    const uint32_t *d_start0, const uint32_t *d_unit_last,
+                    const uint32_t *d_probe, uint64_t probe_values, const uint64_t *d_probe_ptr /* nq + 1 */,
+                    const uint32_t *d_qlist, uint64_t nq,
+                    uint32_t *d_out, uint64_t out_values, uint64_t *d_out_ptr /* nq + 1 */,
+                    uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
+                    void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- values at list positions of a resident index -----------------------------
  * tpf_lists_gather answers nq positional reads against a lists stream, delta-1
  * or plain: query k is the positions d_pos[d_pos_ptr[k] .. d_pos_ptr[k+1]) of

@@ -66,13 +66,43 @@ struct ItemHdr
 {
     unsigned long long bad; // first refused query k, or a code past nq of the entry's own (~0: none)
     uint32_t nitems;
-    uint32_t spare;         // the intersection: nhits = d_out_ptr[nq]
+    uint32_t spare;         // the intersection: nhits = d_out_ptr[nq]; the union: its misses
 };
 
 // go / no-go of everything after the plan: nothing was refused
 __device__ __forceinline__ bool items_go(const ItemHdr * h) { return h->bad == ~0ull; }
 
 constexpr uint32_t kItemNone = 0xFFFFFFFFu; // unit word / list word: the request index names nothing
+
+// What the lookup kernels of the intersection read and leave (k_ix_dec /
+// k_ix_tails, p4_lists_intersect.hip; the union runs them too).  Result word
+// of the intersection's lookup: p inside the unit for a member, else kItemNone.
+// Of the union's (EVERY): for every probe value that has a unit, the lower
+// bound q of the value over the unit (0 .. 256) in bits 0-8 and kIxFound for a
+// member; kItemNone stays where no unit holds the value.
+constexpr uint32_t kIxQ = 0x1FFu;
+constexpr uint32_t kIxFound = 0x200u;
+
+struct IxArgs
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    uint64_t nunits;
+    const uint64_t * ptr;
+    const uint32_t * list_unit;
+    const uint32_t * start0;
+    const uint32_t * unit_last; // the skip table (values, never indices)
+    const uint32_t * probe;
+    uint64_t pv;                // probe_values
+    const ItemHdr * hdr;        // spare: the entry's own total
+    const uint32_t * pu;        // per probe value: source unit | kRecTail, or kItemNone
+    const uint32_t * pl;        // per probe value: target list, or kItemNone
+    const uint32_t * ihead;     // per item: its first probe index ...
+    const uint32_t * iend;      // ... and one past its last
+    uint32_t * res;             // per probe value: the result word (above)
+    unsigned long long * err;
+};
 
 } // namespace tpf::dev
 
@@ -162,6 +192,12 @@ hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const u
                                   const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
                                   uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
                                   uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+// the intersection's plan and its lookup (full blocks, tails) for other entries: `every` runs the EVERY
+// form of the lookup (dev::kIxFound above); pu / pl / ihead / iend / res as the item layer below leaves them
+hipError_t launch_ix_plan(const uint64_t * ptr, const uint32_t * list_unit, uint64_t nlists, uint64_t nunits, const uint32_t * unit_last,
+                          const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
+                          dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s);
+hipError_t launch_ix_lookup(const dev::IxArgs & A, bool every, hipStream_t s);
 // the item layer the intersection and the gather share (p4_lists_items.hip).  pu / pl: per request index
 // its source unit | kRecTail and its list, or kItemNone (the entry's plan).
 // launch_items_reset: d_err and the header's verdict in one launch.
@@ -183,6 +219,20 @@ hipError_t launch_lists_gather(const uint8_t * in, uint64_t in_bytes, const uint
                                const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0,
                                const uint32_t * unit_last, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
                                const uint32_t * qlist, uint64_t nq, uint32_t * out, void * ws, unsigned long long * err, hipStream_t s);
+// the sorted union of probe values with resident lists (p4_lists_union.hip;
+// DESIGN.md 4.16).  Passes: the intersection's plan, items and lookup (EVERY:
+// q and the member flag of every probe value) -> miss flags and their run scan
+// -> plan over the QUERIES (n_j + M_k, the units) and two run scans -> heads
+// (the verdict, d_out_ptr, the virtual units of the targeted lists) -> misses
+// (v to slot L + M, L to the per-query array mlb) -> full blocks -> tails (each
+// list value shifted by the misses at or before it) -> the hits' pidx.  Sized
+// by nq, probe_values and out_values alone.
+size_t lists_union_workspace(uint64_t nq, uint64_t probe_values, uint64_t out_values);
+hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                              const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
+                              const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
+                              uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
+                              uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // postings appended to the lists of a resident index (p4_lists_append.hip;
 // DESIGN.md 4.13).  Passes: plan (one thread per output list: the checks, what
 // of its old tail is staged, its new units) -> four run scans -> heads (the

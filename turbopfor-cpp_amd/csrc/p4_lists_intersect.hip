@@ -21,6 +21,7 @@ namespace tpf::dev
 
 constexpr uint32_t kIxMiss = kItemNone; // result word before the hits pass: not a member
 constexpr uint32_t kIxHit = 0x100u;     // result word after the hits pass: bits 0-7 p, bit 8 hit, bits 16-22 hits before it in its run
+// (EVERY, the union's lookup: every probe value of an item gets q | kIxFound, p4_lists.h)
 
 // Full blocks: items per wave and chunks in flight.  A wave waits for its
 // item's probe values once per block (that load sits behind the chunk loads in
@@ -28,27 +29,6 @@ constexpr uint32_t kIxHit = 0x100u;     // result word after the hits pass: bits
 // k_un_dec's 16 blocks per wave; DESIGN.md 4.11 has both timings.
 constexpr uint32_t kIxRun = 4;
 constexpr uint32_t kIxNC = 4;
-
-struct IxArgs
-{
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * ptr;
-    const uint32_t * list_unit;
-    const uint32_t * start0;
-    const uint32_t * unit_last; // the skip table (values, never indices)
-    const uint32_t * probe;
-    uint64_t pv;                // probe_values
-    const ItemHdr * hdr;        // spare = nhits, d_out_ptr[nq]
-    const uint32_t * pu;        // per probe value: source unit | kRecTail, or kItemNone
-    const uint32_t * pl;        // per probe value: target list, or kItemNone
-    const uint32_t * ihead;     // per item: its first probe index ...
-    const uint32_t * iend;      // ... and one past its last
-    uint32_t * res;             // per probe value: p inside the unit, or kIxMiss
-    unsigned long long * err;
-};
 
 // Plan.  One thread per QUERY: check_queries (p4_lists_dev.h).  One thread per
 // PROBE INDEX: its query by a search over d_probe_ptr, that query's own checks
@@ -105,7 +85,10 @@ __global__ __launch_bounds__(256) void k_ix_plan(const uint64_t * __restrict ptr
 // The probe values [h, e) of one item against the 256 values the wave has just
 // decoded into `vals` (entries past the unit's count hold 0xFFFFFFFF), 64 at a
 // time: a lower bound over the block and an equality check, so a reported hit
-// is an equality whatever the block holds.
+// is an equality whatever the block holds.  EVERY (the union's lookup): the
+// lower bound q, clamped to cnt, is recorded for every value, a member's with
+// kIxFound.
+template <bool EVERY>
 __device__ __forceinline__ void ix_test(const uint32_t * vals, uint32_t cnt, const uint32_t * __restrict probe, uint32_t * __restrict res,
                                         uint32_t h, uint32_t e, uint32_t t)
 {
@@ -119,7 +102,11 @@ __device__ __forceinline__ void ix_test(const uint32_t * vals, uint32_t cnt, con
 #pragma unroll
             for (uint32_t step = 128u; step != 0u; step >>= 1)
                 pos += vals[pos + step - 1u] < v ? step : 0u;
-            res[i] = (pos < cnt && vals[pos] == v) ? pos : kIxMiss;
+            const bool hit = pos < cnt && vals[pos] == v;
+            if constexpr (EVERY)
+                res[i] = umin32(pos, cnt) | (hit ? kIxFound : 0u);
+            else
+                res[i] = hit ? pos : kIxMiss;
         }
     }
 }
@@ -131,7 +118,7 @@ __device__ __forceinline__ void ix_test(const uint32_t * vals, uint32_t cnt, con
 // list < nlists and list_unit[list] <= su < list_unit[list + 1] <= nunits for
 // every value it gave a unit.  Where k_un_dec stores the block, this keeps it
 // in 1 KB of LDS per wave.
-template <uint32_t RUN, uint32_t NC, int MINW>
+template <uint32_t RUN, uint32_t NC, int MINW, bool EVERY>
 __global__ __launch_bounds__(256, MINW) void k_ix_dec(const IxArgs A)
 {
     __shared__ uint32_t slots[4][kSlotBytes / 4];
@@ -193,7 +180,7 @@ __global__ __launch_bounds__(256, MINW) void k_ix_dec(const IxArgs A)
             decode_full_unit<true>(P, c, jj, slot, scr, uni(starts[wv][jj]), t, x, badmask);
             reinterpret_cast<u32x4 *>(vals[wv])[t] = x;
             wave_lds_sync();
-            ix_test(vals[wv], 256u, A.probe, A.res, uni(itemh[wv][jj]), uni(iteme[wv][jj]), t);
+            ix_test<EVERY>(vals[wv], 256u, A.probe, A.res, uni(itemh[wv][jj]), uni(iteme[wv][jj]), t);
             wave_lds_sync();
         });
         report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
@@ -204,7 +191,7 @@ __global__ __launch_bounds__(256, MINW) void k_ix_dec(const IxArgs A)
 // Tails: every wave owns kRunDefault consecutive ITEMS with the generic
 // decoder's pipeline, as k_un_tails does for selections; lane t holds item
 // first + t when its unit is its list's p4Enc32 tail, n % 256 values.
-template <uint32_t NC>
+template <uint32_t NC, bool EVERY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ix_tails(const IxArgs A)
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ix
         for (uint32_t q = 0; q < 4; ++q)
             vals[wv][t + 64u * q] = t + 64u * q < cj ? x.v[q] : 0xFFFFFFFFu;
         wave_lds_sync();
-        ix_test(vals[wv], cj, A.probe, A.res, rl(ih, jj), rl(ie, jj), t);
+        ix_test<EVERY>(vals[wv], cj, A.probe, A.res, rl(ih, jj), rl(ie, jj), t);
         wave_lds_sync();
     });
     report_bad_units(A.err, badmask, su, t);
@@ -365,6 +352,41 @@ struct IxWs
 // nq sizes no array: the queries are read where they lie
 size_t lists_intersect_workspace(uint64_t /*nq*/, uint64_t probe_values) { return IxWs(nullptr, probe_values).bytes; }
 
+hipError_t launch_ix_plan(const uint64_t * ptr, const uint32_t * list_unit, uint64_t nlists, uint64_t nunits, const uint32_t * unit_last,
+                          const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
+                          dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s)
+{
+    hipLaunchKernelGGL(dev::k_ix_plan, dim3(flat_grid(std::max(nq, pv), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, unit_last,
+                       probe, pv, probe_ptr, qlist, nq, hdr, pu, pl);
+    return hipGetLastError();
+}
+
+namespace
+{
+template <bool EVERY>
+hipError_t ix_lookup(const dev::IxArgs & A, uint32_t dgrid, uint32_t igrid, hipStream_t s)
+{
+    hipLaunchKernelGGL((dev::k_ix_dec<dev::kIxRun, dev::kIxNC, dev::kListsMinW, EVERY>), dim3(dgrid), dim3(256), 0, s, A);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((dev::k_ix_tails<dev::kTailsNC, EVERY>), dim3(igrid), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+} // namespace
+
+hipError_t launch_ix_lookup(const dev::IxArgs & A, bool every, hipStream_t s)
+{
+    const uint64_t pv = A.pv;
+    // one wave per kRunDefault items: at least one workgroup for an empty probe
+    const uint32_t igrid = static_cast<uint32_t>(std::max<uint64_t>(1, (pv + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault)));
+    // the cap is one item per probe value, a dense probe holds hundreds of times fewer: at most kListsMinW
+    // workgroups per CU, whose waves stride over the real items (k_ix_tails: a wave per 16 items of the cap)
+    const uint32_t dgrid = static_cast<uint32_t>(std::max<uint64_t>(
+        1, std::min<uint64_t>((pv + 4u * dev::kIxRun - 1u) / (4u * dev::kIxRun), grid_cap(s, dev::kListsMinW))));
+    return every ? ix_lookup<true>(A, dgrid, igrid, s) : ix_lookup<false>(A, dgrid, igrid, s);
+}
+
 hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
                                   const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
                                   const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
@@ -380,29 +402,18 @@ hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const u
         return hipErrorInvalidValue;
     const IxWs W(ws, pv);
     const uint64_t nruns = (pv + 63u) / 64u;
-    // one wave per 64 probe indices, one wave per kRunDefault items: at least one workgroup for an empty probe
+    // one wave per 64 probe indices: at least one workgroup for an empty probe
     const uint32_t rgrid = static_cast<uint32_t>(std::max<uint64_t>(1, (nruns + 3u) / 4u));
-    const uint32_t igrid = static_cast<uint32_t>(std::max<uint64_t>(1, (pv + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault)));
     hipError_t e = launch_items_reset(err, W.hdr, s);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_ix_plan, dim3(flat_grid(std::max(nq, pv), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, unit_last,
-                       probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_ix_plan(ptr, list_unit, nlists, nunits, unit_last, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
         return e;
     if ((e = launch_items(pv, W.hdr, W.pu, W.pl, W.scani, W.ihead, W.iend, W.res, s)) != hipSuccess)
         return e;
     const dev::IxArgs A{in, in_bytes, off, nunits, ptr, list_unit, start0, unit_last, probe, pv, W.hdr, W.pu, W.pl, W.ihead, W.iend,
                         W.res, err};
-    // the cap is one item per probe value, a dense probe holds hundreds of times fewer: at most kListsMinW
-    // workgroups per CU, whose waves stride over the real items (k_ix_tails: a wave per 16 items of the cap)
-    const uint32_t dgrid = static_cast<uint32_t>(std::max<uint64_t>(
-        1, std::min<uint64_t>((pv + 4u * dev::kIxRun - 1u) / (4u * dev::kIxRun), grid_cap(s, dev::kListsMinW))));
-    hipLaunchKernelGGL((dev::k_ix_dec<dev::kIxRun, dev::kIxNC, dev::kListsMinW>), dim3(dgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_ix_tails<dev::kTailsNC>), dim3(igrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_ix_lookup(A, false, s)) != hipSuccess)
         return e;
     hipLaunchKernelGGL(dev::k_ix_hits, dim3(rgrid), dim3(256), 0, s, pv, W.hdr, W.res, W.scanh.tot);
     if ((e = hipGetLastError()) != hipSuccess)

@@ -170,6 +170,13 @@ def lib():
             L.tpf_lists_intersect.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
                                               c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_lists_intersect.restype = ctypes.c_int
+        # the union with a resident index: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_lists_union"):
+            L.tpf_lists_union_workspace_size.argtypes = [c_u64, c_u64, c_u64]
+            L.tpf_lists_union_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_union.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
+                                          c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_union.restype = ctypes.c_int
         # values at list positions of a resident index: absent from older builds loaded through TPF_LIB
         if hasattr(L, "tpf_lists_gather"):
             L.tpf_lists_gather_workspace_size.argtypes = [c_u64, c_u64]
@@ -866,6 +873,50 @@ def lists_intersect(packed, offsets, list_ptr, list_unit, unit_last, probe, prob
     _check(L.tpf_lists_intersect(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
                                  _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
                                  out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
+
+
+# ---- union with a resident index (include/turbopfor_gpu.h tpf_lists_union) ----
+LISTS_NONE = 0xFFFFFFFF  # TPF_LISTS_NONE: pidx of a value the probe does not hold, tpos of one the list does not hold
+
+
+def lists_union(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0=None, out=None, out_ptr=None,
+                pidx=None, tpos=None, err=None, ws=None):
+    """The sorted union of probe doc ids with their target lists: query k is
+    the strictly ascending values probe[probe_ptr[k]:probe_ptr[k+1]] (int32
+    CUDA tensor read as uint32; probe_ptr: int64 CUDA tensor [nq + 1],
+    non-decreasing) merged with list qlist[k] (int32 CUDA tensor [nq]) of a
+    resident delta-1 lists stream.  packed / offsets / list_ptr / list_unit /
+    start0 / unit_last: as lists_intersect.  The union of query k lands at
+    out[out_ptr[k]:out_ptr[k+1]], ascending, so (out, out_ptr) is the probe of
+    the next call of a k-term OR; the first probe is a decn256v32_lists_select
+    decode.  out: int32 CUDA tensor whose numel() is the capacity in values,
+    REQUIRED: a capacity that always suffices is probe.numel() plus the lengths
+    of the targeted lists, which lie in list_ptr on the device, and reading
+    them back would synchronise -- the caller, who built the index, knows them
+    (err == nunits + nq: out_ptr[nq] is what to allocate).  out_ptr: int64
+    CUDA tensor [nq + 1], written; pidx / tpos: optional int32 CUDA tensors of
+    out's capacity, written when passed: the index into probe of a value the
+    probe holds and the position in the target list of a value the list holds,
+    LISTS_NONE otherwise; err: optional int64 CUDA tensor [1] (-1 = clean).
+    The workspace is allocated here unless ws is large enough.  Asynchronous:
+    no device-to-host read.  Returns (out, out_ptr)."""
+    import torch
+
+    if out is None:
+        raise ValueError("lists_union: out is required (its numel() is the capacity; sizing it here would read list_ptr back)")
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nq = qlist.numel()
+    if out_ptr is None:
+        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_union_workspace_size(nq, probe.numel(), out.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_lists_union(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
+                             _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
+                             out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
 
 
