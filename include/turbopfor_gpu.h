@@ -178,6 +178,19 @@ int tpf_p4d1enc256v32_batch(const uint32_t *d_in, uint64_t nblocks, const uint32
  * p4d1enc128v32_scalar.cpp:12) and the next unit of a chained list starts
  * from value n-1.  Of a decoded unit the first n values are specified
  * (tests/test_gpu_formats32.py holds all of this).
+ * TPF_FMT_128V64 with n below 128 follows the same contract on both of its
+ * base layouts: without delta-1 a plain-mode block carries the low b bits of
+ * the caller's slots n .. 127 -- in the pair-swapped 128v32 layout at
+ * b <= 32, in the horizontal 64-bit pack at b > 32, the whole words at width
+ * 64 (header 63) -- as the reference's p4Enc128v64 does, which hands the
+ * caller's array to bitpack128v64Scalar and that packs 128 slots
+ * (p4enc128v64_scalar.cpp:167); no other mode, and no length, depends on
+ * those slots.  With delta-1, and in the base payload of every bitmap or
+ * vbyte block, the padding bits are zero (the reference packs its
+ * uninitialised stack there, p4enc128v64_scalar.cpp:59,
+ * p4d1enc128v64_scalar.cpp) and the next unit of a chained list starts from
+ * value n-1 (tests/test_gpu_formats64.py).  TPF_FMT_256V64 batches hold
+ * whole units (n = 256).
  * Values are uint32 or uint64 as the family requires.  D1 (delta-1): starts
  * per unit, or NULL = one chained list (encode: start0 then the previous
  * unit's last input, value n-1; decode requires starts). */

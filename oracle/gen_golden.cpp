@@ -814,6 +814,316 @@ static void gen32_bx0(Writer & w, Fmt32 f, uint64_t seed, const std::vector<unsi
         }
 }
 
+// ------------------- 128v64 / 256v64 at every n, mode and base layout
+// One class of block per record: the mode (plain, bitmap patch, raw or
+// compressed vbyte, constant, all zero) and the base width, which picks the
+// base layout -- b = 0 (no base), 1..32 (the pair-swapped 128v32 layout),
+// 33..62 (the horizontal 64-bit pack) -- with width 63 and 64 (header 63)
+// for plain and constant.  A draw that the cost model encodes otherwise is
+// drawn again.
+enum Kind64
+{
+    K_ZERO,
+    K_CONST,
+    K_PLAIN,
+    K_BITMAP,
+    K_VBRAW,
+    K_VBCOMP
+};
+
+struct Class64
+{
+    Kind64 kind;
+    unsigned b; // base width wanted (K_CONST, K_PLAIN: the width, up to 64)
+    bool wide_patch; // K_BITMAP: bx > 32
+};
+
+static bool isClass64(const uint8_t * enc, const Class64 & c)
+{
+    const unsigned h = enc[0], hb = h & 0x3Fu, want = c.b >= 63u ? 63u : c.b;
+    // an exception block may settle on a neighbouring base width: the same layout counts
+    const bool lay = c.b == 0u ? hb == 0u : c.b <= 32u ? (hb >= 1u && hb <= 32u) : (hb >= 33u && hb <= 62u);
+    switch (c.kind)
+    {
+        case K_ZERO:
+            return h == 0u;
+        case K_CONST:
+            return (h & 0xC0u) == 0xC0u && hb == want;
+        case K_PLAIN:
+            return (h & 0xC0u) == 0u && hb == want;
+        case K_BITMAP:
+            return (h & 0xC0u) == 0x80u && lay && (enc[1] > 32u) == c.wide_patch;
+        default:
+            return (h & 0xC0u) == 0x40u && lay && ((enc[2u + 16u * hb] == 0xFFu) == (c.kind == K_VBRAW));
+    }
+}
+
+static std::vector<uint64_t> baseOf(Rng & r, unsigned n, unsigned b)
+{
+    std::vector<uint64_t> v(n, 0ull);
+    if (b == 0u)
+        return v;
+    for (auto & x : v)
+        x = r.range(0, b == 64u ? ~0ull : ((1ull << b) - 1ull));
+    v[r.range(0, n - 1)] |= 1ull << (b - 1); // width exactly b
+    return v;
+}
+
+static std::vector<unsigned> shuffled(Rng & r, unsigned n)
+{
+    std::vector<unsigned> pos(n);
+    for (unsigned i = 0; i < n; ++i)
+        pos[i] = i;
+    for (unsigned i = 0; i + 1 < n; ++i)
+        std::swap(pos[i], pos[i + r.range(0, n - 1 - i)]);
+    return pos;
+}
+
+// One draw of the class (n values, the gaps of the list when delta-1).
+// wstep rotates the widths of the long vbyte forms through b + 8 .. 64.
+static std::vector<uint64_t> draw64(Rng & r, unsigned n, const Class64 & c, unsigned & wstep)
+{
+    const unsigned b = c.b;
+    std::vector<uint64_t> v;
+    switch (c.kind)
+    {
+        case K_ZERO:
+            return std::vector<uint64_t>(n, 0ull);
+        case K_CONST:
+            return std::vector<uint64_t>(n, ofWidth(r, b));
+        case K_PLAIN:
+            return baseOf(r, n, b);
+        case K_BITMAP:
+        {
+            // n/6 exceptions (at least one; fewer would go to vbyte) of one width: a patch of bx <= 32 or bx > 32 bits.
+            // A few values over a horizontal base pay for the bitmap only over the
+            // narrowest base and with the widest patch.
+            const unsigned bb = (n < 16u && b > 32u) ? 33u : b;
+            v = baseOf(r, n, bb);
+            const unsigned hi = c.wide_patch ? 64u : std::min(64u, bb + 32u);
+            const unsigned lo = n < 16u ? hi - 1u : c.wide_patch ? bb + 33u : bb + std::min(12u, 64u - bb);
+            const unsigned w = static_cast<unsigned>(r.range(lo, hi));
+            const auto pos = shuffled(r, n);
+            for (unsigned i = 0; i < std::max(1u, n / 6u) && i + 1 < n; ++i)
+                v[pos[i]] = ofWidth(r, w);
+            return v;
+        }
+        case K_VBRAW:
+        {
+            // one to three values 8..24 bits over the base: fewer than 5 exceptions are never compressed
+            v = baseOf(r, n, b);
+            const auto pos = shuffled(r, n);
+            if (n < 9u)
+            {
+                // the bitmap is one byte: vbyte pays only for one value 10..15 bits over a
+                // narrow base beside one 62..64 bits wide (tests/v64_inputs.py VB_MIN_N64)
+                v[pos[0]] = ofWidth(r, b + static_cast<unsigned>(r.range(10, 15)));
+                v[pos[1]] = ofWidth(r, static_cast<unsigned>(r.range(62, 64)));
+                return v;
+            }
+            const unsigned k = static_cast<unsigned>(r.range(1, 3));
+            for (unsigned i = 0; i < k; ++i)
+                v[pos[i]] = ofWidth(r, b + static_cast<unsigned>(r.range(8, std::min(24u, 64u - b))));
+            return v;
+        }
+        default:
+        {
+            v = baseOf(r, n, b);
+            const auto pos = shuffled(r, n);
+            if (n < 40u)
+            {
+                // small n: 4 .. 12 exceptions (at most 2n/5) whose excess has exactly 7 bits and
+                // one outlier 15 bits over the base (a 3-byte marker)
+                const unsigned xn = static_cast<unsigned>(r.range(4, std::min(12u, 2u * n / 5u)));
+                for (unsigned i = 0; i < xn; ++i)
+                    v[pos[i]] = (v[pos[i]] & (b ? (1ull << b) - 1ull : 0ull)) | (r.range(64, 127) << b);
+                v[pos[xn]] = ofWidth(r, b + 15u);
+                return v;
+            }
+            // between n/8 and n/3 exceptions with a one-byte marker, one to three of them long
+            const unsigned xn = static_cast<unsigned>(r.range((n + 7) / 8, n / 3));
+            for (unsigned i = 0; i < xn; ++i)
+                v[pos[i]] = (v[pos[i]] & (b ? (1ull << b) - 1ull : 0ull)) | (r.range(1, 149) << b);
+            const unsigned big = static_cast<unsigned>(r.range(1, 3));
+            for (unsigned i = 0; i < big; ++i)
+            {
+                const unsigned span = 64u - (b + 8u) + 1u;
+                v[pos[i]] = ofWidth(r, b + 8u + (wstep * 5u) % span);
+                ++wstep;
+            }
+            return v;
+        }
+    }
+}
+
+// A block of the class: drawn until the reference encodes it that way.
+static std::vector<uint64_t> block64(Rng & r, unsigned n, const Class64 & c, unsigned & wstep, unsigned idx)
+{
+    std::vector<uint8_t> enc(128 * 10 + 4096);
+    for (unsigned t = 0; t < 400; ++t)
+    {
+        std::vector<uint64_t> v = draw64(r, n, c, wstep);
+        std::vector<uint64_t> in(128 + 64, 0ull);
+        std::copy(v.begin(), v.end(), in.begin());
+        std::fill(enc.begin(), enc.end(), 0);
+        sc::p4Enc128v64(in.data(), n, enc.data());
+        if (isClass64(enc.data(), c))
+            return v;
+    }
+    std::fprintf(stderr, "class not reached: kind %d b %u n %u\n", int(c.kind), c.b, n);
+    die("64 class", idx);
+    return {};
+}
+
+// Which classes exist at n: one value is all zero or constant; vbyte needs
+// n >= 5, over a horizontal base n >= 9, and compressed vbyte n >= 10
+// (tests/v64_inputs.py).
+static bool exists64(const Class64 & c, unsigned n)
+{
+    if (c.kind == K_ZERO || c.kind == K_CONST)
+        return true;
+    if (c.kind == K_VBRAW)
+        return n >= (c.b > 32u ? 9u : 5u);
+    if (c.kind == K_VBCOMP)
+        return n >= 10u;
+    return n >= 2u;
+}
+
+// The classes of one n; `rot` alternates the width of the header-63 records
+// (63 / 64), the patch width of the bitmap records (bx <= 32 / bx > 32 where
+// the base leaves room) and the horizontal base widths through 33..62.
+static std::vector<Class64> classes64(unsigned rot)
+{
+    const unsigned top = 63u + (rot & 1u);
+    const unsigned hb[4] = {33u, 40u, 62u, 35u};
+    const unsigned h = hb[rot & 3u], hx = hb[(rot + 1u) & 3u];
+    const bool wp = (rot & 1u) != 0u;
+    return {
+        {K_ZERO, 0, false},       {K_CONST, 5, false},         {K_CONST, top, false},      {K_PLAIN, (rot & 1u) ? 32u : 9u, false},
+        {K_PLAIN, h, false},      {K_PLAIN, top, false},       {K_BITMAP, 0, wp},          {K_BITMAP, 7, !wp},
+        {K_BITMAP, hx == 62u ? 50u : hx, false}, {K_VBRAW, 0, false}, {K_VBRAW, 6, false}, {K_VBRAW, hx == 62u ? 41u : hx, false},
+        {K_VBCOMP, 0, false},     {K_VBCOMP, 3, false},        {K_VBCOMP, hx == 62u ? 36u : hx == 33u ? 38u : hx, false}, // (b = 33 loses to b + 7 by byte rounding at n = 10)
+    };
+}
+
+static std::vector<uint64_t> asList(const std::vector<uint64_t> & gaps, uint64_t start)
+{
+    std::vector<uint64_t> v(gaps.size());
+    uint64_t cur = start;
+    for (size_t i = 0; i < gaps.size(); ++i)
+        v[i] = (cur += gaps[i] + 1ull);
+    return v;
+}
+
+static void gen64s_128(Writer & w, uint64_t seed)
+{
+    Rng r(seed);
+    unsigned wstep = 0, rot = 0;
+    for (unsigned n : {1u, 2u, 5u, 7u, 8u, 9u, 10u, 31u, 32u, 33u, 63u, 64u, 65u, 100u, 127u})
+    {
+        for (unsigned d1 = 0; d1 < 2; ++d1)
+            for (const Class64 & c : classes64(rot + d1))
+            {
+                if (!exists64(c, n))
+                    continue;
+                std::vector<uint64_t> v = block64(r, n, c, wstep, w.count);
+                // delta-1: the block's values are the list's gaps; one list per n wraps 2^64
+                const uint64_t st = c.kind == K_PLAIN ? ~0ull - 1000ull : r.next() >> 1;
+                add64_short(w, d1 ? asList(v, st) : v, d1 != 0, d1 ? st : 0ull, true);
+            }
+        ++rot;
+    }
+}
+
+// decode-only: header 0x80 | b with bx == 0 (p4d1dec128v64_scalar.cpp:211,
+// :298), which the encoder never emits: b = 8 (vertical base), 40
+// (horizontal) and 63 (= 64)
+static void gen64s_bx0(Writer & w, uint64_t seed)
+{
+    Rng r(seed);
+    for (unsigned b : {8u, 40u, 63u})
+        for (unsigned n : {128u, 100u, 7u})
+        {
+            const unsigned bb = 16u * (b == 63u ? 64u : b);
+            std::vector<uint8_t> enc(2 + bb + 64, 0);
+            enc[0] = static_cast<uint8_t>(0x80u | b);
+            for (unsigned i = 0; i < bb; ++i)
+                enc[2 + i] = static_cast<uint8_t>(r.next());
+            std::vector<uint64_t> dec(256 + 64, 0);
+            if (sc::p4Dec128v64(enc.data(), n, dec.data()) != enc.data() + 2 + bb)
+                die("128v64 decode-only end pointer", w.count);
+            w.record(2u, n, 0, 8u, dec.data(), enc.data(), 2 + bb);
+            if (sc::p4D1Dec128v64(enc.data(), n, dec.data(), ~0ull - 77ull) != enc.data() + 2 + bb)
+                die("128v64 decode-only D1 end pointer", w.count);
+            w.record(3u, n, ~0ull - 77ull, 8u, dec.data(), enc.data(), 2 + bb);
+        }
+}
+
+// 256v64 units of n values: a 128v64 block of min(n, 128) values and one of
+// the rest, each of a class of its own, paired so that each half carries
+// each base layout.
+static void gen64s_256(Writer & w, uint64_t seed)
+{
+    Rng r(seed);
+    unsigned wstep = 0;
+    const Class64 Z{K_ZERO, 0, false}, C{K_CONST, 21, false}, C63{K_CONST, 63, false}, C64{K_CONST, 64, false};
+    const Class64 PV{K_PLAIN, 17, false}, PH{K_PLAIN, 34, false}, P63{K_PLAIN, 63, false}, P64{K_PLAIN, 64, false};
+    const Class64 B0{K_BITMAP, 0, true}, BV{K_BITMAP, 9, false}, BH{K_BITMAP, 37, false};
+    const Class64 R0{K_VBRAW, 0, false}, RV{K_VBRAW, 4, false}, RH{K_VBRAW, 33, false};
+    const Class64 V0{K_VBCOMP, 0, false}, VV{K_VBCOMP, 2, false}, VH{K_VBCOMP, 35, false};
+    const std::vector<std::pair<Class64, Class64>> pairs = {{PV, PH}, {PH, PV}, {BV, BH}, {BH, BV}, {RV, RH},   {RH, RV}, {VV, VH},
+                                                            {VH, VV}, {Z, P63},  {P64, C63}, {C, Z},  {C64, C}, {B0, R0}, {R0, V0},
+                                                            {V0, B0}};
+    // a class that does not exist at the block's n falls back: zero, constant, constant of width 64
+    const Class64 small[3] = {Z, C, C64};
+    for (unsigned n : {1u, 100u, 128u, 129u, 200u, 255u, 256u})
+        for (unsigned d1 = 0; d1 < 2; ++d1)
+            for (size_t p = 0; p < pairs.size(); ++p)
+            {
+                if (d1 && (p % 2u))
+                    continue; // delta-1 twins: every other pair, one order of each layout pair
+                std::vector<uint64_t> v;
+                for (unsigned c0 = 0; c0 < n; c0 += 128u)
+                {
+                    const unsigned bn = std::min(n - c0, 128u);
+                    Class64 c = c0 ? pairs[p].second : pairs[p].first;
+                    if (!exists64(c, bn))
+                        c = small[p % 3u];
+                    const auto blk = block64(r, bn, c, wstep, w.count);
+                    v.insert(v.end(), blk.begin(), blk.end());
+                }
+                const uint64_t st = p == 0 ? ~0ull - 1000ull : r.next() >> 1;
+                add64_short(w, d1 ? asList(v, st) : v, d1 != 0, d1 ? st : 0ull, false);
+            }
+    // decode-only: the bx == 0 header in the first half, then in the second
+    for (unsigned half = 0; half < 2; ++half)
+    {
+        std::vector<uint8_t> enc;
+        for (unsigned k = 0; k < 2; ++k)
+        {
+            const unsigned b = k == half ? (half ? 40u : 8u) : (half ? 12u : 44u);
+            if (k == half)
+            {
+                enc.push_back(static_cast<uint8_t>(0x80u | b));
+                enc.push_back(0);
+            }
+            else
+                enc.push_back(static_cast<uint8_t>(b));
+            for (unsigned i = 0; i < 16u * b; ++i)
+                enc.push_back(static_cast<uint8_t>(r.next()));
+        }
+        const uint32_t len = static_cast<uint32_t>(enc.size());
+        enc.resize(enc.size() + 64, 0);
+        std::vector<uint64_t> dec(256 + 64, 0);
+        if (sc::p4Dec256v64(enc.data(), 256, dec.data()) != enc.data() + len)
+            die("256v64 decode-only end pointer", w.count);
+        w.record(2u, 256, 0, 8u, dec.data(), enc.data(), len);
+        if (sc::p4D1Dec256v64(enc.data(), 256, dec.data(), ~0ull - 77ull) != enc.data() + len)
+            die("256v64 decode-only D1 end pointer", w.count);
+        w.record(3u, 256, ~0ull - 77ull, 8u, dec.data(), enc.data(), len);
+    }
+}
+
 // Hand-made decode-only vectors: valid streams the encoder never emits.
 static void genDecodeOnly(Writer & w)
 {
@@ -886,6 +1196,17 @@ int main(int argc, char ** argv)
         gen32_vbyte(w, FH32, 0x33, {127u, 256u, 100u, 200u}, 16u);
         gen32_bx0(w, FH32, 0x34, {127u, 256u, 100u});
         w.save(dir + "/g32vb.bin");
+    }
+    {
+        Writer w;
+        gen64s_128(w, 0x128066);
+        gen64s_bx0(w, 0x128067);
+        w.save(dir + "/g128v64s.bin");
+    }
+    {
+        Writer w;
+        gen64s_256(w, 0x256066);
+        w.save(dir + "/g256v64s.bin");
     }
     return 0;
 }

@@ -85,7 +85,8 @@ def test_perblock_mode_query_and_set(lib):
 
 @pytest.mark.parametrize("fname,fmt", [("g32.bin", "32"), ("g128v32.bin", "128v32"), ("g256v32.bin", "256v32"),
                                        ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64"),
-                                       ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32")])
+                                       ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32"),
+                                       ("g128v64s.bin", "128v64"), ("g256v64s.bin", "256v64")])
 def test_framing_matches_golden(lib, fname, fmt):
     lib.tpf_block_size.restype = ctypes.c_uint64
     lib.tpf_block_size.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint,

@@ -15,6 +15,7 @@ import pytest
 import h64_inputs
 import oracle_lib
 import p4_modes
+import v64_inputs
 
 torch = pytest.importorskip("torch")
 tpf = pytest.importorskip("turbopfor_amd")
@@ -295,3 +296,45 @@ def test_dec64_position_past_block_flagged():
     assert int(err.item()) == bad_unit
     got = out.cpu().numpy().view(np.uint64).reshape(nu, width)
     np.testing.assert_array_equal(got[:bad_unit], vals[:bad_unit])
+
+
+@pytest.mark.parametrize("fmt", ["128v64", "256v64"])
+def test_chained64_every_mode(fmt):
+    """The 1029 every-mode units of test_gpu_formats64.py at n = 128 (256v64:
+    514 pairs of them) as one chained list from 2^64 - 4096, whose gaps are up
+    to 64 bits wide: plain and constant units of width 63 and 64, every
+    exception mode over the vertical and over the horizontal base layout
+    (b > 32: phase A's lane path declines those units to the wave decoder),
+    all-zero units, and -- on a second pass -- every plain unit rewritten to
+    the decode-only 0x80 | b, bx = 0 header.  Both passes of
+    tpf_d1dec64_chained and the D1Chain64 sums + decode parse every mode on
+    their own: values exact, d_total = sum(gap + 1) mod 2^64, d_err clean."""
+    c = v64_inputs.v64_case("128v64", 128, True)
+    v64_inputs.check_census(c)
+    assert min(c.modes[m] for m in ("zero", "const63", "plain63", "plain_h", "bitmap_h", "vb_raw_h", "vb_comp_h")) >= 10
+    per = 2 if fmt == "256v64" else 1
+    nu = c.nu // per
+    width = 128 * per
+    vals = c.vals[: nu * per].reshape(nu, width)
+    with np.errstate(over="ignore"):
+        want_total = int((c.gaps[: nu * per].ravel() + np.uint64(1)).sum(dtype=np.uint64))
+    bp, bo, kv, kh = v64_inputs.as_bx0("128v64", c.packed, c.off, 128)
+    assert kv >= 10 and kh >= 10
+    for name, pk, off in (("oracle", c.packed, c.off), ("bx0", bp, bo)):
+        off = off[: nu * per + 1: per].astype(np.int64)
+        packed = torch.from_numpy(pk[: int(off[-1])].copy()).to(DEV)
+        offs = torch.from_numpy(off).to(DEV)
+        err = torch.zeros(1, dtype=torch.int64, device=DEV)
+        out = tpf.dec64_chained(fmt, packed, offs, nu, start0=v64_inputs.CHAIN_START0, err=err)
+        torch.cuda.synchronize()
+        assert int(err.item()) == -1, name
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), vals, err_msg=name)
+        chain = tpf.D1Chain64(fmt, packed, offs, nu)
+        total = chain.sums(err=err)
+        torch.cuda.synchronize()
+        assert int(err.item()) == -1, name
+        assert int(total.item()) & M64 == want_total, name
+        out = chain.decode(v64_inputs.CHAIN_START0, err=err)
+        torch.cuda.synchronize()
+        assert int(err.item()) == -1, name
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), vals, err_msg=name)

@@ -43,7 +43,8 @@ def perblock_mode(request):
 
 @pytest.mark.parametrize("fname,fmt", [("g32.bin", "32"), ("g128v32.bin", "128v32"), ("g256v32.bin", "256v32"),
                                        ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64"),
-                                       ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32")])
+                                       ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32"),
+                                       ("g128v64s.bin", "128v64"), ("g256v64s.bin", "256v64")])
 def test_per_block_mirrors_match_golden(fname, fmt, perblock_mode):
     L = capi()
     wide = fmt in ("64", "128v64", "256v64")

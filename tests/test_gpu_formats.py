@@ -22,7 +22,8 @@ U64 = (1 << 64) - 1
 
 FAMILIES = [("g32.bin", "32"), ("g128v32.bin", "128v32"), ("g256v32.bin", "256v32"),
             ("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g64.bin", "64"),
-            ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32")]
+            ("g32vb.bin", "32"), ("g128v32s.bin", "128v32"), ("g256v32s.bin", "256v32"),
+            ("g128v64s.bin", "128v64"), ("g256v64s.bin", "256v64")]
 
 
 def to_dev(arr, wide):

@@ -6,10 +6,38 @@ import pytest
 import golden_io
 import oracle_lib
 import p4_modes
+import v64_inputs
 
 FAMILIES = [("g256v32.bin", "256v32"), ("g128v32.bin", "128v32"), ("g32.bin", "32"),
             ("g256v64.bin", "256v64"), ("g128v64.bin", "128v64"), ("g64.bin", "64"),
-            ("g256v32s.bin", "256v32"), ("g128v32s.bin", "128v32"), ("g32vb.bin", "32")]
+            ("g256v32s.bin", "256v32"), ("g128v32s.bin", "128v32"), ("g32vb.bin", "32"),
+            ("g256v64s.bin", "256v64"), ("g128v64s.bin", "128v64")]
+V64_FILES = [("g128v64.bin", "128v64"), ("g256v64.bin", "256v64"), ("g128v64s.bin", "128v64"), ("g256v64s.bin", "256v64")]
+
+
+def blocks64(fmt, r):
+    """The 128v64 blocks of a 128v64 / 256v64 record: [(block's n, Block64)]."""
+    out, pos = [], 0
+    for bn in v64_inputs.block_ns(fmt, r.n):
+        blk = p4_modes.parse64(r.enc, pos, bn, 128)
+        out.append((bn, blk))
+        pos = blk.end
+    assert pos == len(r.enc)
+    return out
+
+
+def pinned_bytes64(fmt, r):
+    """A record's bytes with the base payload of every block shorter than 128
+    values zeroed: what the reference pins even where its padding bits came
+    from its stack -- header, bx / xn, bitmap, patch bits, vbyte stream and
+    positions.  Applied to the reference's bytes and to the oracle's."""
+    def strip(enc):
+        enc = bytearray(enc)
+        for bn, blk in blocks64(fmt, r):
+            if bn < 128:
+                enc[blk.base[0]: blk.base[1]] = bytes(blk.base[1] - blk.base[0])
+        return bytes(enc)
+    return strip
 
 
 @pytest.mark.parametrize("fname,fmt", FAMILIES)
@@ -22,6 +50,10 @@ def test_oracle_matches_golden(fname, fmt):
             if r.padding_unpinned:
                 # padding slots follow the zero convention: same length, same values back
                 assert len(enc) == len(r.enc), f"{fname} record {i}: encoded length differs"
+                if fmt in ("128v64", "256v64"):
+                    # everything outside the short blocks' base payload is the reference's
+                    strip = pinned_bytes64(fmt, r)
+                    assert strip(enc) == strip(r.enc), f"{fname} record {i}: bytes outside the base payload differ"
                 back, used = oracle_lib.decode(fmt, enc, r.n, d1=r.d1, start=r.start)
                 assert used == len(enc)
                 np.testing.assert_array_equal(back, r.values, err_msg=f"{fname} record {i} (own bytes)")
@@ -41,6 +73,105 @@ def test_short_64bit_units_are_pinned():
         assert len(short) >= 50
         pinned = [r for r in short if not r.padding_unpinned]
         assert len(pinned) >= len(short) // 2, (fname, len(pinned), len(short))
+
+
+def _class64(blk):
+    """Block64.split with the exception modes over no base (b = 0) apart."""
+    return blk.mode + "_0" if blk.mode in ("bitmap", "vb_raw", "vb_comp") and blk.b == 0 else blk.split
+
+
+UNFLAGGED64 = ("zero", "const", "const63", "plain_v", "plain_h", "plain63", "bitmap_0", "vb_raw_0", "vb_comp_0")
+
+
+@pytest.mark.parametrize("fname,fmt", V64_FILES)
+def test_flag_rule_of_64bit_units(fname, fmt):
+    """Where the reference's 128v64 bytes depend on its uninitialised stack
+    (flag 4, found by encoding after a 0x00 and after a 0xA5 fill of the
+    stack): exactly the records with a block of fewer than 128 values that is
+    either in bitmap or vbyte mode with b >= 1 -- base[] is a stack array of
+    which p4Enc128v64PayloadExceptions fills n slots and bitpack128v64Scalar
+    packs 128 (p4enc128v64_scalar.cpp:59, :113, :130), with or without
+    delta-1 -- or a delta-1 block in plain mode, whose n deltas sit in a stack
+    array too (p4d1enc128v64_scalar.cpp).  An exception block with b = 0 packs
+    no base at all, so it is pinned even with delta-1.  No zero, constant or
+    non-delta-1 plain record is flagged.  In the every-mode files at least
+    half of the short records without delta-1 are byte-pinned, and so are at
+    least two blocks of every class that can be."""
+    recs = [r for r in golden_io.load(fname) if not r.decode_only]
+    full = v64_inputs.WIDTH[fmt]
+    unflagged = dict.fromkeys(UNFLAGGED64, 0)
+    for i, r in enumerate(recs):
+        want = False
+        for bn, blk in blocks64(fmt, r):
+            if bn == 128:
+                continue
+            hit = (blk.mode in ("bitmap", "vb_raw", "vb_comp") and blk.b >= 1) or (r.d1 and blk.mode in ("plain", "plain63"))
+            want |= hit
+            if not hit and not r.d1:
+                unflagged[_class64(blk)] += 1
+        assert r.padding_unpinned == want, (fname, i, r.n, r.d1, [b.split for _, b in blocks64(fmt, r)])
+    short = [r for r in recs if r.n < full and not r.d1]
+    assert len(short) >= 40
+    assert 2 * sum(not r.padding_unpinned for r in short) >= len(short), fname
+    assert any(r.padding_unpinned for r in recs)  # the rule is exercised
+    if fname.endswith("s.bin"):
+        assert min(unflagged.values()) >= 2, unflagged
+
+
+def test_golden64s_cover_every_class():
+    """g128v64s.bin holds, at every n of its list, every class the encoder can
+    produce there (v64_inputs.required_modes: each mode over the vertical and
+    over the horizontal base layout) plain and as the gaps of a delta-1 list,
+    the exception modes also over no base (b = 0); across the file bitmap
+    patches of bx <= 32 and bx > 32, plain and constant blocks of width
+    exactly 63 and exactly 64, compressed vbyte from the smallest n that has
+    it with every marker length 1..9, a list that wraps 2^64, and the
+    decode-only bx = 0 header at b = 8, 40 and 63 with n = 128, 100 and 7.
+    g256v64s.bin holds every class in each half, and the bx = 0 header in
+    either half."""
+    recs = golden_io.load("g128v64s.bin")
+    by_n, lens, bx, top, bx0 = {}, set(), set(), set(), set()
+    for r in recs:
+        (_, blk), = blocks64("128v64", r)
+        assert (blk.mode == "bx0") == r.decode_only
+        if r.decode_only:
+            bx0.add((blk.b, r.n, r.d1))
+            continue
+        by_n.setdefault((r.n, r.d1), set()).add(_class64(blk))
+        lens.update(blk.lens)
+        if blk.mode == "bitmap":
+            bx.add(blk.bx > 32)
+        if blk.b == 63 and not r.d1:
+            top.add((blk.mode, int(r.values.max()).bit_length()))
+    assert sorted({n for n, _ in by_n}) == [1, 2, 5, 7, 8, 9, 10, 31, 32, 33, 63, 64, 65, 100, 127]  # 5, 9, 10: where the vbyte classes begin
+    for (n, d1), have in by_n.items():
+        need = set(v64_inputs.required_modes(n))
+        if n >= 2:
+            need.add("bitmap_0")
+        if n >= v64_inputs.VB_MIN_N64:
+            need.add("vb_raw_0")
+        if n >= v64_inputs.VB_COMP_MIN_N64:
+            need.add("vb_comp_0")
+        assert have == need, (n, d1, need ^ have)
+    assert lens == set(range(1, 10)) and bx == {False, True}
+    assert top == {("plain63", 63), ("plain63", 64), ("const63", 63), ("const63", 64)}
+    assert bx0 == {(b, n, d1) for b in (8, 40, 63) for n in (128, 100, 7) for d1 in (False, True)}
+    assert any(r.d1 and r.start > (1 << 64) - 2000 and r.values[-1] < r.start for r in recs)  # wraps 2^64
+    recs = golden_io.load("g256v64s.bin")
+    halves, lens, bx0 = [set(), set()], set(), set()
+    for r in recs:
+        for h, (bn, blk) in enumerate(blocks64("256v64", r)):
+            if r.decode_only:
+                bx0.add((h, blk.mode))
+                continue
+            halves[h].add(_class64(blk))
+            lens.update(blk.lens)
+    assert {r.n for r in recs} == {1, 100, 128, 129, 200, 255, 256}
+    for h in halves:
+        assert h == set(v64_inputs.required_modes(128)) | {"bitmap_0", "vb_raw_0", "vb_comp_0"}, h
+    assert lens == set(range(1, 10))
+    assert {(0, "bx0"), (1, "bx0")} <= bx0
+    assert any(r.d1 and r.start > (1 << 64) - 2000 and r.values[-1] < r.start for r in recs)
 
 
 def test_short_32bit_units_are_pinned():
