@@ -728,6 +728,95 @@ int tpf_lists_union(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_of
                     uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
                     void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- difference with a resident index -----------------------------------------
+ * tpf_lists_difference answers nq exclusions (AND NOT) against a delta-1 lists
+ * stream: query k is the probe values d_probe[d_probe_ptr[k] ..
+ * d_probe_ptr[k+1]), tested against list j = d_qlist[k].  It returns the values
+ * that are NOT in list j, with where they would be inserted.  The argument list
+ * is tpf_lists_intersect's, argument for argument: a caller switches operator
+ * by switching the symbol.  "A AND NOT B AND NOT C" and the deleted-documents
+ * filter ("result AND NOT tombstones") are the call chained on the device:
+ * d_out and d_out_ptr of one call are d_probe and d_probe_ptr of the next.
+ *   - The index and the probe: exactly the arguments of tpf_lists_intersect --
+ *     the stream, its offsets, d_list_ptr, d_list_unit, d_start0 (NULL means
+ *     0), the skip table d_unit_last (required); d_probe_ptr (nq + 1 entries)
+ *     non-decreasing, not necessarily from 0; nothing of d_probe outside
+ *     [d_probe_ptr[0], d_probe_ptr[nq]) is read.  Empty segments are allowed
+ *     anywhere; the same list may be the target of many queries.  d_out must
+ *     not overlap d_probe.
+ *   - Definition: tpf_lists_union's.  Probe index i of query k, with value v
+ *     and target j of n = n_j values, is a HIT or a MISS exactly as
+ *     tpf_lists_union defines them, and L(i) is the union's: u is the first
+ *     unit of [ua, ub) with d_unit_last[u] >= v; with no such unit L(i) = n and
+ *     i is a miss; otherwise q is the branch-free lower bound of v over the
+ *     decoded unit, held to cnt, L(i) = min(256 (u - ua) + q, n), and i is a
+ *     hit iff q < cnt and the value at q equals v.
+ *       The misses of query k go to d_out[d_out_ptr[k] .. d_out_ptr[k+1]) in
+ *     probe order; d_out_ptr[0] = 0: the output is dense and itself a CSR
+ *     array.  d_out_pidx (optional) gets i, the index into d_probe.
+ *     d_out_tpos (optional) gets L(i): the number of list values below v,
+ *     which is also the list position of the first value above v -- the
+ *     advance(target) / next-doc-at-or-after answer of a posting-list cursor
+ *     -- or n_j when there is none.  n_j is NOT a valid tpf_lists_gather
+ *     position: drop such entries before reading successors.
+ *   - The probe need not be sorted or free of duplicates, as with the
+ *     intersection: the lookup is per value and every occurrence is reported.
+ *     An ascending segment gives an ascending output segment, a valid probe of
+ *     the next tpf_lists_intersect, tpf_lists_union or tpf_lists_difference.
+ *   - Complement law.  On any input that passes the query checks and has no
+ *     parse error, a probe index of [d_probe_ptr[0], d_probe_ptr[nq]) is
+ *     reported by tpf_lists_difference iff tpf_lists_intersect on the same
+ *     arguments does not report it: both use the same search.  So for a list
+ *     that ascends without wrapping mod 2^32, with a correct table, this is
+ *     exactly "v is not in list j".  Outside that precondition (a list that
+ *     wraps, a wrong table) which indices are reported is unspecified, apart
+ *     from the law itself, and every access stays in bounds: the table holds
+ *     values, never indices.
+ *   - Output bounds: nothing is written at or past d_out + out_values (the same
+ *     for d_out_pidx and d_out_tpos), and nothing outside a query's slice.
+ *     d_out is only 4-byte aligned.  Misses never exceed the probe, so
+ *     out_values = probe_values always suffices.
+ *   - Cost: no kernel and no workspace array is sized by nlists or nunits.
+ *     Grids and the workspace (a few words per probe value; nq sizes nothing)
+ *     are sized on the host from probe_values alone.  Stream bytes are read
+ *     only at units a probe value lands in; a value past its list's last value,
+ *     or aimed at an empty list, costs no decode.  d_list_ptr and d_list_unit
+ *     are read by the plan as the intersection reads them, and again for
+ *     misses only, when d_out_tpos is passed.  Ten launches for a probe of up
+ *     to 262,144 values and twelve beyond (each of the two run scans then
+ *     takes a second launch), two for nq == 0: decided on the host by
+ *     probe_values, whatever the queries.
+ *   - Errors through d_err (optional; UINT64_MAX = clean), the intersection's,
+ *     code for code; the lowest code is the one reported:
+ *       < nunits        the lowest SOURCE unit, among the units decoded, whose
+ *                       parse disagrees with its offsets; which values of such
+ *                       a unit are reported is unspecified but in bounds;
+ *       nunits + k      the first query k refused by any check
+ *                       tpf_lists_intersect makes on a query: nothing is
+ *                       written to d_out, d_out_ptr, d_out_pidx or d_out_tpos;
+ *       nunits + nq     the misses do not fit out_values: nothing is written to
+ *                       d_out, d_out_pidx or d_out_tpos, but d_out_ptr is
+ *                       filled completely, so d_out_ptr[nq] is what to allocate.
+ *   - TPF_EINVAL (decided before any device call): with nq non-zero a null
+ *     d_in, d_off, d_list_ptr, d_list_unit, d_unit_last, d_probe_ptr, d_qlist,
+ *     d_out_ptr or d_ws; a null d_probe or d_out while probe_values or
+ *     out_values is non-zero; ws_bytes below
+ *     tpf_lists_difference_workspace_size(nq, probe_values); nlists, nunits, nq
+ *     or probe_values above 0x7FFFFFFF.  nq == 0 is a successful no-op that
+ *     writes d_out_ptr[0] = 0 and sets d_err to clean.
+ *   - Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy; the call can be captured in a graph.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_lists_difference_workspace_size(uint64_t nq, uint64_t probe_values);
+int tpf_lists_difference(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                         const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                         const uint32_t *d_start0, const uint32_t *d_unit_last,
+                         const uint32_t *d_probe, uint64_t probe_values, const uint64_t *d_probe_ptr /* nq + 1 */,
+                         const uint32_t *d_qlist, uint64_t nq,
+                         uint32_t *d_out, uint64_t out_values, uint64_t *d_out_ptr /* nq + 1 */,
+                         uint32_t *d_out_pidx /* optional */, uint32_t *d_out_tpos /* optional */,
+                         void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- values at list positions of a resident index -----------------------------
  * tpf_lists_gather answers nq positional reads against a lists stream, delta-1
  * or plain: query k is the positions d_pos[d_pos_ptr[k] .. d_pos_ptr[k+1]) of

@@ -716,6 +716,35 @@ int tpf_lists_union(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_union");
 }
 
+size_t tpf_lists_difference_workspace_size(uint64_t nq, uint64_t probe_values)
+{
+    return tpf::lists_difference_workspace(nq, probe_values);
+}
+
+int tpf_lists_difference(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                         const uint32_t * d_list_unit, uint64_t nlists, const uint32_t * d_start0, const uint32_t * d_unit_last,
+                         const uint32_t * d_probe, uint64_t probe_values, const uint64_t * d_probe_ptr, const uint32_t * d_qlist,
+                         uint64_t nq, uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr, uint32_t * d_out_pidx,
+                         uint32_t * d_out_tpos, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || probe_values > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL, "tpf_lists_difference: nlists, nunits, nq and probe_values are limited to 0x7FFFFFFF");
+    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_unit_last || !d_probe_ptr || !d_qlist || !d_out_ptr || !d_ws))
+        return fail(TPF_EINVAL, "tpf_lists_difference: null pointer");
+    if ((probe_values && !d_probe) || (out_values && !d_out))
+        return fail(TPF_EINVAL, "tpf_lists_difference: null d_probe or d_out with a non-zero size");
+    if (nq && ws_bytes < tpf_lists_difference_workspace_size(nq, probe_values))
+        return fail(TPF_EINVAL, "tpf_lists_difference: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // d_err is reset by the launcher, together with its workspace header
+    hipError_t e = tpf::launch_lists_difference(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last,
+                                                d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr,
+                                                d_out_pidx, d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_difference");
+}
+
 size_t tpf_lists_gather_workspace_size(uint64_t nq, uint64_t pos_values)
 {
     return tpf::lists_gather_workspace(nq, pos_values);

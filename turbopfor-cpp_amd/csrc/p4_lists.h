@@ -66,7 +66,7 @@ struct ItemHdr
 {
     unsigned long long bad; // first refused query k, or a code past nq of the entry's own (~0: none)
     uint32_t nitems;
-    uint32_t spare;         // the intersection: nhits = d_out_ptr[nq]; the union: its misses
+    uint32_t spare;         // the intersection: nhits = d_out_ptr[nq]; the union and the difference: their misses
 };
 
 // go / no-go of everything after the plan: nothing was refused
@@ -233,6 +233,18 @@ hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint6
                               const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
                               uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
                               uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+// the probe values that are NOT in resident lists (p4_lists_difference.hip;
+// DESIGN.md 4.17).  Passes: the intersection's plan, items and lookup (EVERY:
+// q and the member flag of every probe value that has a unit) -> miss flags
+// (a value without a unit is a miss by the plan's word) and their run scan ->
+// compaction (d_out_ptr, the verdict, the scatter of value, probe index and
+// L).  Sized by probe_values alone, as the intersection.
+size_t lists_difference_workspace(uint64_t nq, uint64_t probe_values);
+hipError_t launch_lists_difference(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
+                                   const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
+                                   const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
+                                   uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
+                                   uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // postings appended to the lists of a resident index (p4_lists_append.hip;
 // DESIGN.md 4.13).  Passes: plan (one thread per output list: the checks, what
 // of its old tail is staged, its new units) -> four run scans -> heads (the

@@ -177,6 +177,13 @@ def lib():
             L.tpf_lists_union.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
                                           c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_lists_union.restype = ctypes.c_int
+        # the difference with a resident index: absent from older builds loaded through TPF_LIB
+        if hasattr(L, "tpf_lists_difference"):
+            L.tpf_lists_difference_workspace_size.argtypes = [c_u64, c_u64]
+            L.tpf_lists_difference_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_difference.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
+                                               c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_difference.restype = ctypes.c_int
         # values at list positions of a resident index: absent from older builds loaded through TPF_LIB
         if hasattr(L, "tpf_lists_gather"):
             L.tpf_lists_gather_workspace_size.argtypes = [c_u64, c_u64]
@@ -917,6 +924,44 @@ def lists_union(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_pt
     _check(L.tpf_lists_union(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
                              _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
                              out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
+
+
+# ---- difference with a resident index (include/turbopfor_gpu.h tpf_lists_difference) ----
+def lists_difference(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0=None, out=None, out_ptr=None,
+                     pidx=None, tpos=None, err=None, ws=None):
+    """Which probe doc ids are NOT in their target lists (AND NOT): query k is
+    the values probe[probe_ptr[k]:probe_ptr[k+1]] (int32 CUDA tensor read as
+    uint32, sorted for the least work; probe_ptr: int64 CUDA tensor [nq + 1],
+    non-decreasing) tested against list qlist[k] (int32 CUDA tensor [nq]) of a
+    resident delta-1 lists stream.  The arguments, defaults and allocation
+    rules are lists_intersect's.  The values list qlist[k] does not hold land
+    at out[out_ptr[k]:out_ptr[k+1]] in probe order, so (out, out_ptr) is the
+    probe of the next lists_intersect, lists_union or lists_difference.  out:
+    int32 CUDA tensor whose numel() is the capacity in values (default:
+    probe.numel(), which always suffices, so the default stays asynchronous);
+    out_ptr: int64 CUDA tensor [nq + 1], written; pidx / tpos: optional int32
+    CUDA tensors of out's capacity, written when passed: the value's index
+    into probe, and the number of list values below it -- the position of the
+    first list value above it, or the list's length when there is none (not a
+    lists_gather position); err: optional int64 CUDA tensor [1] (-1 = clean).
+    Returns (out, out_ptr)."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1
+    nq = qlist.numel()
+    if out is None:
+        out = torch.empty(probe.numel(), dtype=torch.int32, device=packed.device)
+    if out_ptr is None:
+        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws_bytes = int(L.tpf_lists_difference_workspace_size(nq, probe.numel()))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    _check(L.tpf_lists_difference(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
+                                  _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
+                                  out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
 
 
