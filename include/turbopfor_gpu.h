@@ -991,6 +991,113 @@ int tpf_lists_append(
                           uint32_t *d_unit_last_out /* units_cap; required when d1 != 0, ignored otherwise */,
                           void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- postings deleted from a resident index -----------------------------------
+ * tpf_lists_remove shortens the lists of a lists stream: list j of the result is
+ * L_j without the values at the list-relative positions a query names.  Every
+ * unit of a list before the one that holds its first removed position keeps its
+ * bytes, and so does every list that loses nothing; only the suffix of a list
+ * from that unit on is decoded, compacted and encoded again.  Positions, not doc
+ * ids: the same removals delete from a doc-id stream (d1 != 0) and from the
+ * frequency stream stored in parallel over the same directory (d1 == 0).  Every
+ * table the readers need comes out of the same call, as with tpf_lists_append.
+ *   - The old index: as tpf_lists_append reads it; with d1 != 0 the skip table
+ *     d_unit_last is required.  d_start0 has nlists entries (NULL = 0; ignored
+ *     with d1 == 0).  With nunits == 0 d_in and d_off are not read.
+ *   - The removals: segment k is d_pos[d_pos_ptr[k] .. d_pos_ptr[k+1]) and names
+ *     positions of list d_qlist[k], strictly ascending within the segment.
+ *     d_qlist is strictly ascending, so a list is targeted at most once.
+ *     d_pos_ptr (nq + 1 entries) is non-decreasing and need not start at 0;
+ *     pos_values is the readable length of d_pos and nothing of d_pos outside
+ *     [d_pos_ptr[0], d_pos_ptr[nq]) is read.  Empty segments are allowed
+ *     anywhere.  d_out_tpos, d_out_ptr and d_qlist of a tpf_lists_intersect call
+ *     whose queries ascend by list and whose probe segments ascend feed the call
+ *     unchanged.
+ *   - The result: list ids are stable -- a list that loses everything stays, as
+ *     an empty list.  d_list_ptr_out[0] = 0; d_list_unit_out is what
+ *     tpf_lists_unit_base gives for the new lengths, its last entry the result's
+ *     unit count nunits_out.  For an old stream written by this library's
+ *     encoders d_out and d_off_out[0 .. nunits_out] are byte for byte and offset
+ *     for offset what tpf_p4nenc256v32_lists writes for the shortened lists with
+ *     the same d1 and d_start0 (with d1: given a correct d_unit_last).  With d1,
+ *     d_unit_last_out[0 .. nunits_out) is what tpf_lists_unit_last gives for the
+ *     new stream.  The outputs must not overlap the inputs: the call is out of
+ *     place and the caller swaps buffers.
+ *   - What is read of the old stream: for a targeted list with a non-empty
+ *     segment and first removed position p0, u0 = p0 / 256.  Units [0, u0) of the
+ *     list are copied and never parsed; units [u0, end) are decoded, from
+ *     d_start0[j] when u0 == 0, else from d_unit_last of unit u0 - 1.  A list
+ *     with no removals, its tail included, is copied and never parsed.  Interior
+ *     offsets of copied ranges are carried over shifted and not checked; the ends
+ *     of each copied byte range are held against in_bytes.  The table holds
+ *     values, never indices: a wrong table gives wrong bytes and never an
+ *     out-of-range access.
+ *   - Staging: the call stages s_j = |L_j| - 256 u0 values per affected list and
+ *     stage_values is the capacity of their sum.  The sum of |L_j| over the
+ *     targeted lists always suffices.  The workspace, the decode and the encoder
+ *     are sized by nq and stage_values, the per-list arrays by nlists; only the
+ *     stitch pass and the offsets pass are sized by the whole index.
+ *   - Capacities: units_cap is the capacity of d_off_out (units_cap + 1 entries)
+ *     and of d_unit_last_out; nunits_out <= nunits always, so units_cap = nunits
+ *     suffices.  The stream can grow (the merge of two deltas can widen a
+ *     block): tpf_lists_remove_bound = in_bytes +
+ *     tpf_p4nenc256v32_lists_bound(stage_values, nq) always suffices for out_cap.
+ *     Both are advice, not preconditions: nothing is written at or past a
+ *     capacity.
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed; the lowest code is the one reported:
+ *       < nunits                  the lowest decoded unit whose offsets lie outside
+ *                                 the stream or whose parse disagrees with them;
+ *                                 what is written is unspecified but in bounds;
+ *       nunits + j                the first list j that fails a structure check:
+ *                                 list_ptr[j+1] < list_ptr[j]; a d_list_unit span
+ *                                 different from the unit count of |L_j|;
+ *                                 list_unit[j+1] > nunits; a copied byte range with
+ *                                 off[lo] > off[hi] or off[hi] > in_bytes.  Nothing
+ *                                 is written, in any output;
+ *       nunits + nlists + k       the first refused query k: d_qlist[k] >= nlists;
+ *                                 d_qlist[k] <= d_qlist[k-1]; pos_ptr[k+1] <
+ *                                 pos_ptr[k]; pos_ptr[k+1] > pos_values; a position
+ *                                 >= |L_j|; a position not above the one before it
+ *                                 in its segment.  Nothing is written;
+ *       nunits + nlists + nq      the staged values exceed stage_values: only
+ *                                 d_list_ptr_out and d_list_unit_out are written,
+ *                                 completely;
+ *       nunits + nlists + nq + 1  nunits_out > units_cap: the two directories only;
+ *       nunits + nlists + nq + 2  the stream is longer than out_cap: everything
+ *                                 is written except d_out, so
+ *                                 d_off_out[nunits_out] is what to allocate.
+ *   - TPF_EINVAL (decided before any device call): a null d_off_out,
+ *     d_list_ptr_out or d_list_unit_out; with nlists non-zero a null d_list_ptr,
+ *     d_list_unit, d_ws or d_out (with out_cap non-zero), a null d_in or d_off
+ *     with nunits non-zero, a null d_unit_last (with nunits non-zero) or
+ *     d_unit_last_out when d1 != 0, a null d_pos_ptr or d_qlist with nq non-zero,
+ *     a null d_pos with nq and pos_values non-zero; ws_bytes below
+ *     tpf_lists_remove_workspace_size(nunits, nlists, nq, pos_values,
+ *     stage_values); nunits, nlists, nq, pos_values, stage_values, units_cap or
+ *     stage_values / 256 + nq + 1 above 0x7FFFFFFF.  nlists == 0 is a successful
+ *     no-op that writes d_list_ptr_out[0] = 0, d_list_unit_out[0] = 0,
+ *     d_off_out[0] = 0 and a clean d_err; nq == 0 with nlists != 0 is a plain
+ *     restitch of the index.
+ *   - Cost: the stitch pass moves the whole index once, as the append's.
+ *     Everything is enqueued on `stream`: no host synchronisation and no
+ *     device-to-host copy; at most 36 launches, their number and their grids
+ *     fixed by the arguments' sizes, not their contents.
+ * d_ws: device workspace, at least 8-byte aligned. */
+uint64_t tpf_lists_remove_bound(uint64_t in_bytes, uint64_t nq, uint64_t stage_values);
+size_t   tpf_lists_remove_workspace_size(uint64_t nunits, uint64_t nlists, uint64_t nq,
+                                         uint64_t pos_values, uint64_t stage_values);
+int tpf_lists_remove(
+    /* the old index */ const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                        const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                        int d1, const uint32_t *d_start0 /* nlists, or NULL = 0 */,
+                        const uint32_t *d_unit_last /* required when d1 != 0 */,
+    /* the removals */  const uint32_t *d_pos, uint64_t pos_values, const uint64_t *d_pos_ptr /* nq + 1 */,
+                        const uint32_t *d_qlist /* nq */, uint64_t nq, uint64_t stage_values,
+    /* the new index */ uint8_t *d_out, uint64_t out_cap, uint64_t *d_off_out /* units_cap + 1 */, uint64_t units_cap,
+                        uint64_t *d_list_ptr_out /* nlists + 1 */, uint32_t *d_list_unit_out /* nlists + 1 */,
+                        uint32_t *d_unit_last_out /* units_cap; required when d1 != 0 */,
+                        void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

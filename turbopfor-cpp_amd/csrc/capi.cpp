@@ -827,6 +827,58 @@ int tpf_lists_append(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_append");
 }
 
+// ---- postings deleted from a resident index (p4_lists_remove.hip)
+uint64_t tpf_lists_remove_bound(uint64_t in_bytes, uint64_t nq, uint64_t stage_values)
+{
+    return in_bytes + tpf_p4nenc256v32_lists_bound(stage_values, nq);
+}
+
+size_t tpf_lists_remove_workspace_size(uint64_t nunits, uint64_t nlists, uint64_t nq, uint64_t pos_values, uint64_t stage_values)
+{
+    (void)nunits, (void)pos_values; // nothing of the workspace is sized by them
+    return tpf::lists_remove_workspace(nlists, nq, stage_values);
+}
+
+int tpf_lists_remove(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                     const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last,
+                     const uint32_t * d_pos, uint64_t pos_values, const uint64_t * d_pos_ptr, const uint32_t * d_qlist, uint64_t nq,
+                     uint64_t stage_values, uint8_t * d_out, uint64_t out_cap, uint64_t * d_off_out, uint64_t units_cap,
+                     uint64_t * d_list_ptr_out, uint32_t * d_list_unit_out, uint32_t * d_unit_last_out, void * d_ws, size_t ws_bytes,
+                     uint64_t * d_err, void * stream)
+{
+    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || pos_values > 0x7FFFFFFFull
+        || stage_values > 0x7FFFFFFFull || units_cap > 0x7FFFFFFFull || stage_values / 256u + nq + 1u > 0x7FFFFFFFull)
+        return fail(TPF_EINVAL,
+                    "tpf_lists_remove: nunits, nlists, nq, pos_values, stage_values, units_cap and stage_values / 256 + nq + 1 are "
+                    "limited to 0x7FFFFFFF");
+    if (!d_off_out || !d_list_ptr_out || !d_list_unit_out)
+        return fail(TPF_EINVAL, "tpf_lists_remove: null pointer");
+    if (nlists && (!d_list_ptr || !d_list_unit || !d_ws || (out_cap && !d_out)))
+        return fail(TPF_EINVAL, "tpf_lists_remove: null pointer");
+    if (nlists && nunits && (!d_in || !d_off))
+        return fail(TPF_EINVAL, "tpf_lists_remove: null pointer (the old index)");
+    if (nlists && d1 && (!d_unit_last_out || (nunits && !d_unit_last)))
+        return fail(TPF_EINVAL,
+                    "tpf_lists_remove: null d_unit_last or d_unit_last_out (delta-1 needs the skip table of tpf_lists_unit_last)");
+    if (nlists && nq && (!d_pos_ptr || !d_qlist))
+        return fail(TPF_EINVAL, "tpf_lists_remove: null d_pos_ptr or d_qlist with a non-zero nq");
+    if (nlists && nq && pos_values && !d_pos)
+        return fail(TPF_EINVAL, "tpf_lists_remove: null d_pos with a non-zero pos_values");
+    if (nlists && ws_bytes < tpf_lists_remove_workspace_size(nunits, nlists, nq, pos_values, stage_values))
+        return fail(TPF_EINVAL, "tpf_lists_remove: workspace too small");
+    if (int rc = check_device())
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = prep_err(d_err, s))
+        return rc;
+    hipError_t e = tpf::launch_lists_remove(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
+                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_pos, pos_values, d_pos_ptr, d_qlist,
+                                            nlists ? nq : 0u, stage_values, d_out, out_cap, d_off_out, units_cap, d_list_ptr_out,
+                                            d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
+                                            reinterpret_cast<unsigned long long *>(d_err), s);
+    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_remove");
+}
+
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
 {
     if (int rc = check_device())

@@ -27,7 +27,7 @@ namespace tpf::dev
 constexpr uint32_t kRecTail = 0x80000000u;
 constexpr uint32_t kRecList = 0x7FFFFFFFu;
 
-// bytes of d_out one wave of the append's stitch pass moves (p4_lists_append.hip)
+// bytes of d_out one wave of the stitch pass moves (p4_lists_stitch.h: the append and the remove)
 constexpr uint32_t kListsAppendTile = 16384;
 
 struct ListsHdr
@@ -259,6 +259,22 @@ hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint
                                const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t nlists_out, uint8_t * out,
                                uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out,
                                uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s);
+// postings deleted at list positions of a resident index (p4_lists_remove.hip;
+// DESIGN.md 4.18).  Passes: plan over the QUERIES (the checks, the unit range
+// [u0, end) of every targeted list, its compacted count) and over the positions
+// -> plan over the lists (structure, kept units and bytes) -> five run scans ->
+// the units decode of the ranges (launch_lists_units) -> heads over the queries
+// (the encoder's plan) and over the lists (the verdict, both directories) ->
+// compaction -> the encoder's passes -> segs -> offsets -> stitch
+// (p4_lists_stitch.h), the last three as the append's.  Workspace, decode and
+// encoder are sized by nq and stage_values, the per-list arrays by nlists.
+size_t lists_remove_workspace(uint64_t nlists, uint64_t nq, uint64_t stage_values);
+hipError_t launch_lists_remove(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
+                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
+                               const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr, const uint32_t * qlist, uint64_t nq,
+                               uint64_t stage_values, uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap,
+                               uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out, void * ws, unsigned long long * err,
+                               hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

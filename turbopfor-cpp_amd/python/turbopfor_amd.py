@@ -201,6 +201,14 @@ def lib():
             L.tpf_lists_append.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_u64,
                                            c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
             L.tpf_lists_append.restype = ctypes.c_int
+        if hasattr(L, "tpf_lists_remove"):
+            L.tpf_lists_remove_bound.argtypes = [c_u64, c_u64, c_u64]
+            L.tpf_lists_remove_bound.restype = c_u64
+            L.tpf_lists_remove_workspace_size.argtypes = [c_u64, c_u64, c_u64, c_u64, c_u64]
+            L.tpf_lists_remove_workspace_size.restype = ctypes.c_size_t
+            L.tpf_lists_remove.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp,
+                                           c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
+            L.tpf_lists_remove.restype = ctypes.c_int
         for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
                      "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
                      "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
@@ -1094,4 +1102,63 @@ def lists_append(packed, offsets, list_ptr, list_unit, add, add_ptr, d1=False, s
                               _ptr(start0), _ptr(unit_last), _ptr(add), nadd, _ptr(add_ptr), nlists_out, _ptr(out), out.numel(),
                               _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out), _ptr(ws),
                               ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
+    return out, out_offsets, list_ptr_out, list_unit_out, unit_last_out
+
+
+# ---- postings deleted from a resident index (include/turbopfor_gpu.h tpf_lists_remove) ----
+def lists_remove_bound(in_bytes, nq, stage_values):
+    """A byte capacity that always suffices for lists_remove
+    (tpf_lists_remove_bound: advice, not a precondition)."""
+    return int(lib().tpf_lists_remove_bound(int(in_bytes), int(nq), int(stage_values)))
+
+
+def lists_remove(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, stage_values, d1=False, start0=None, unit_last=None,
+                 out=None, out_offsets=None, units_cap=None, err=None, ws=None, stream=None):
+    """Delete the postings at list positions of a resident index, out of
+    place: list qlist[k] of the result is the old list without the values at
+    positions pos[pos_ptr[k]:pos_ptr[k+1]] (strictly ascending; qlist strictly
+    ascending).  The tpos / out_ptr / qlist of lists_intersect feed it
+    unchanged.  packed / offsets / list_ptr / list_unit / start0 / unit_last:
+    the old index as decn256v32_lists_units reads it (unit_last required with
+    d1).  The units of a list before its first removed position, and every
+    list that loses nothing, are moved as bytes; only the suffix is decoded,
+    compacted and encoded again, so the result is byte for byte
+    encn256v32_lists of the shortened lists.  stage_values: the capacity of
+    the staged suffixes (the sum of the targeted lists' lengths always
+    suffices).  out: uint8 CUDA tensor whose numel() is the byte capacity
+    (default: lists_remove_bound); out_offsets: int64 CUDA tensor [units_cap +
+    1] (default units_cap: the old unit count, which always suffices).  err:
+    optional int64 CUDA tensor [1] (-1 = clean).  stream: a raw HIP stream
+    handle (default: torch's current stream).  Asynchronous: no
+    device-to-host read; the stream's length is
+    out_offsets[list_unit_out[-1]].  Returns (out, out_offsets, list_ptr_out,
+    list_unit_out, unit_last_out or None)."""
+    import torch
+
+    if d1 and unit_last is None and offsets is not None and offsets.numel() > 1:
+        raise ValueError("lists_remove: d1=True needs unit_last (lists_unit_last)")
+    dev = list_ptr.device
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1 if offsets is not None and nlists > 0 else 0
+    in_bytes = packed.numel() if packed is not None else 0
+    nq = qlist.numel() if qlist is not None else 0
+    npos = pos.numel() if pos is not None else 0
+    stage_values = int(stage_values)
+    L = lib()
+    if units_cap is None:
+        units_cap = out_offsets.numel() - 1 if out_offsets is not None else nunits
+    if out_offsets is None:
+        out_offsets = torch.empty(units_cap + 1, dtype=torch.int64, device=dev)
+    if out is None:
+        out = torch.empty(max(lists_remove_bound(in_bytes, nq, stage_values), 1), dtype=torch.uint8, device=dev)
+    list_ptr_out = torch.empty(nlists + 1, dtype=torch.int64, device=dev)
+    list_unit_out = torch.empty(nlists + 1, dtype=torch.int32, device=dev)
+    unit_last_out = torch.empty(max(units_cap, 1), dtype=torch.int32, device=dev) if d1 else None
+    ws_bytes = int(L.tpf_lists_remove_workspace_size(nunits, nlists, nq, npos, stage_values))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _check(L.tpf_lists_remove(_ptr(packed), in_bytes, _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
+                              _ptr(start0), _ptr(unit_last), _ptr(pos), npos, _ptr(pos_ptr), _ptr(qlist), nq, stage_values, _ptr(out),
+                              out.numel(), _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out),
+                              _ptr(ws), ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
     return out, out_offsets, list_ptr_out, list_unit_out, unit_last_out
