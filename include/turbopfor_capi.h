@@ -111,6 +111,17 @@ int64_t tpf_check_offsets(const uint64_t *off, uint64_t nblocks, uint64_t in_byt
  * with its offsets fails the call with TPF_ECORRUPT (tpf_last_error names the
  * block).  Encode writes nblocks + 1 entries to h_off.
  * Encode fails with TPF_EINVAL when the blocks do not fit in out_cap.
+ * tpf_host_enc checks, in this order and on the host before any device is
+ * touched (the same answer with or without a GPU): h_off not NULL (TPF_EINVAL;
+ * h_off[0] = 0 is then written); nblocks == 0 succeeds with nothing else done;
+ * h_vals and h_out not NULL (TPF_EINVAL); (fmt, n) one that tpf_enc_batch
+ * accepts (TPF_EINVAL "unsupported (fmt, n)").  It writes nothing at or past
+ * h_out + out_cap, also when it fails with "out_cap too small" (h_out below
+ * out_cap and h_off are then unspecified).  A failed call of any entry below
+ * leaves the library usable: the next call works.
+ * Every h_* pointer must be dereferenceable by the host CPU (pageable, pinned
+ * or registered host memory): the offsets, and the value before a chunk or
+ * shard cut of a chained D1 list, are read by the CPU, never device memory.
  * Value arrays use the unit strides documented in turbopfor_gpu.h. */
 int tpf_host_dec(int fmt, const uint8_t *h_in, uint64_t in_bytes, const uint64_t *h_off, uint64_t nblocks, unsigned n,
                  void *h_vals, const void *h_starts);
@@ -128,11 +139,16 @@ int tpf_host_dec_multi(const int *devs, int ndev, int fmt, const uint8_t *h_in, 
 /* Encode one host array on several GPUs at once: the blocks are cut into ndev
  * contiguous shards of equal block counts and shard d runs tpf_host_enc's
  * pipeline on device devs[d] from its own thread.  Shard 0 writes straight
- * into h_out; the others into pooled host staging, moved into place (and
+ * into h_out; the others into host scratch (see below), moved into place (and
  * their offsets rebased) once the sizes before them are known.  The bytes
  * and offsets are identical to tpf_host_enc's (a chained D1 list continues
  * across shard cuts: each shard starts from the value before its first
- * block).  Arguments and checks as tpf_host_enc. */
+ * block).  Arguments and checks as tpf_host_enc, with devs not NULL and
+ * 1 <= ndev <= 64 (TPF_EINVAL) checked on the host as well.  When out_cap
+ * holds the sum of the shards' tpf_enc_bound, the later shards are written
+ * inside h_out at provisional offsets before they are moved down: bytes
+ * between h_off[nblocks] and out_cap are then scratch.  Nothing at or past
+ * h_out + out_cap is written. */
 int tpf_host_enc_multi(const int *devs, int ndev, int fmt, const void *h_vals, uint64_t nblocks, unsigned n, int d1,
                        const void *h_starts, uint64_t start0, uint8_t *h_out, uint64_t out_cap, uint64_t *h_off);
 

@@ -154,3 +154,43 @@ def test_host_entries_check_offsets_before_the_device(lib):
     assert b"unsupported" in lib.tpf_last_error()
     assert lib.tpf_host_dec(2, None, u64(4096), good, u64(4), 256, vals, None) == -1
     assert lib.tpf_host_dec_multi(None, 0, 2, data, u64(4096), good, u64(4), 256, vals, None) == -1
+
+
+ENC_BAD_FMT_N = [(0, 0), (3, 0), (99, 0), (2, 0), (2, 257), (1, 129), (4, 129), (5, 100), (99, 5)]
+
+
+def test_host_encoders_check_arguments_before_the_device(lib):
+    """The encode side of "the same answer with or without a GPU": a (fmt, n)
+    that tpf_enc_batch refuses, a null h_vals / h_out / h_off and an ndev
+    outside 1..64 are TPF_EINVAL from tpf_host_enc and tpf_host_enc_multi, on
+    the host, before any device is touched (and before tpf_host_enc divides the
+    chunk size by a unit of 0 values: fmt 0, 3 or an unknown one with n = 0)."""
+    lib.tpf_last_error.restype = ctypes.c_char_p
+    lib.tpf_host_enc.restype = ctypes.c_int
+    lib.tpf_host_enc_multi.restype = ctypes.c_int
+    u64 = ctypes.c_uint64
+    vals = (ctypes.c_uint64 * (256 * 4))()
+    out = (ctypes.c_uint8 * 65536)()
+    off = (ctypes.c_uint64 * 5)()
+    devs = (ctypes.c_int * 65)()
+
+    def enc(fmt, n, v=vals, o=out, f=off):
+        return lib.tpf_host_enc(fmt, v, u64(4), n, 0, None, u64(0), o, u64(65536), f)
+
+    def multi(fmt, n, v=vals, o=out, f=off, d=devs, nd=2):
+        return lib.tpf_host_enc_multi(d, nd, fmt, v, u64(4), n, 0, None, u64(0), o, u64(65536), f)
+
+    for fmt, n in ENC_BAD_FMT_N:
+        for call in (enc, multi):
+            assert call(fmt, n) == -1, (call.__name__, fmt, n, lib.tpf_last_error())
+            assert b"unsupported" in lib.tpf_last_error(), (call.__name__, fmt, n, lib.tpf_last_error())
+    for call in (enc, multi):
+        assert call(2, 256, v=None) == -1, (call.__name__, "h_vals", lib.tpf_last_error())
+        assert call(2, 256, o=None) == -1, (call.__name__, "h_out", lib.tpf_last_error())
+        assert call(2, 256, f=None) == -1, (call.__name__, "h_off", lib.tpf_last_error())
+    assert multi(2, 256, nd=0) == -1, lib.tpf_last_error()
+    assert multi(2, 256, nd=65) == -1, lib.tpf_last_error()
+    assert multi(2, 256, d=None) == -1, lib.tpf_last_error()
+    # nblocks == 0 stays a successful no-op that writes h_off[0] = 0
+    off[0] = 77
+    assert lib.tpf_host_enc(99, None, u64(0), 0, 0, None, u64(0), None, u64(0), off) == 0 and off[0] == 0

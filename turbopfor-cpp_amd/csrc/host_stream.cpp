@@ -447,7 +447,8 @@ int host_dec_impl(int fmt, const uint8_t * h_in, uint64_t in_bytes, const uint64
                 src_in = s;
             }
             hc(hipMemcpyAsync(d_off, st_off, (nb + 1) * 8, hipMemcpyHostToDevice, P.cs), "H2D off");
-            hc(hipMemcpyAsync(d_in, src_in, bytes, r_in.direct ? r_in.up() : hipMemcpyHostToDevice, P.cs), "H2D bytes");
+            if (bytes) // (a chunk of empty blocks -- every offset equal -- has nothing to upload; the kernel reports its first block)
+                hc(hipMemcpyAsync(d_in, src_in, bytes, r_in.direct ? r_in.up() : hipMemcpyHostToDevice, P.cs), "H2D bytes");
             if (h_starts)
             {
                 const void * src_st = static_cast<const uint8_t *>(h_starts) + c0 * es;
@@ -602,6 +603,13 @@ int tpf_host_enc(int fmt, const void * h_vals, uint64_t nblocks, unsigned n, int
         h_off[0] = 0;
         if (nblocks == 0)
             return TPF_OK;
+        // checked on the host before anything touches a device, as
+        // tpf_host_dec does: the same answer with or without a GPU, and no
+        // division by a unit of 0 values below
+        if (!h_vals || !h_out)
+            throw Err(TPF_EINVAL, "tpf_host_enc: null pointer");
+        if (!tpf::fmt_ok(fmt, n))
+            throw Err(TPF_EINVAL, "tpf_host_enc: unsupported (fmt, n)");
         need_device();
         const size_t es = unit_bytes(fmt, n).es, uv = tpf::unit_values(fmt, n);
         const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nblocks, chunk_value_bytes() / (es * uv)));
@@ -716,6 +724,8 @@ int tpf_host_enc_multi(const int * devs, int ndev, int fmt, const void * h_vals,
         h_off[0] = 0;
         if (nblocks == 0)
             return TPF_OK;
+        if (!devs || ndev < 1 || ndev > 64)
+            throw Err(TPF_EINVAL, "tpf_host_enc_multi: need 1..64 devices");
         // validate before any shard reads the caller's array (a chained D1
         // shard reads the value before its first block: with n == 0 or n past
         // the unit that read would leave the array)
@@ -726,8 +736,6 @@ int tpf_host_enc_multi(const int * devs, int ndev, int fmt, const void * h_vals,
         need_device();
         int cnt = 0;
         hc(hipGetDeviceCount(&cnt), "hipGetDeviceCount");
-        if (!devs || ndev < 1 || ndev > 64)
-            throw Err(TPF_EINVAL, "tpf_host_enc_multi: need 1..64 devices");
         for (int d = 0; d < ndev; ++d)
             if (devs[d] < 0 || devs[d] >= cnt)
                 throw Err(TPF_EINVAL, "tpf_host_enc_multi: device " + std::to_string(devs[d]) + " is not visible");
