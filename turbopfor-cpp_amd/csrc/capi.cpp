@@ -47,6 +47,23 @@ int prep_err(uint64_t * d_err, hipStream_t s)
     hipError_t e = tpf::fill_u32(d_err, 0xFFFFFFFFu, 2, s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "init d_err");
 }
+
+// The resident index of an entry point, its arguments in the public order: a
+// plain stream (d1 == 0) has neither starts nor a skip table, whatever the
+// caller passed.
+tpf::ListsIndex lists_index(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                            const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last)
+{
+    return tpf::ListsIndex{.in = d_in,
+                           .in_bytes = in_bytes,
+                           .off = d_off,
+                           .nunits = nunits,
+                           .ptr = d_list_ptr,
+                           .list_unit = d_list_unit,
+                           .nlists = nlists,
+                           .start0 = d1 ? d_start0 : nullptr,
+                           .unit_last = d1 ? d_unit_last : nullptr};
+}
 } // namespace
 
 namespace tpf
@@ -487,8 +504,8 @@ int tpf_p4ndec256v32_lists(const uint8_t * d_in, uint64_t in_bytes, const uint64
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_dec(d_in, in_bytes, d_off, nunits, d_list_ptr, nlists, d1 != 0, d1 ? d_start0 : nullptr, d_out,
-                                         out_values, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, nullptr, nlists, d1, d_start0, nullptr);
+    hipError_t e = tpf::launch_lists_dec(X, d1 != 0, d_out, out_values, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists");
 }
 
@@ -576,8 +593,8 @@ int tpf_p4ndec256v32_lists_select(const uint8_t * d_in, uint64_t in_bytes, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_select(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
-                                            d1 ? d_start0 : nullptr, d_sel, nsel, d_out, out_values, d_out_ptr, d_ws,
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, nullptr);
+    hipError_t e = tpf::launch_lists_select(X, d1 != 0, d_sel, nsel, d_out, out_values, d_out_ptr, d_ws,
                                             reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_select");
 }
@@ -602,8 +619,8 @@ int tpf_lists_unit_last(const uint8_t * d_in, uint64_t in_bytes, const uint64_t 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_unit_last(d_in, in_bytes, d_off, nunits, d_list_ptr, nlists, d_start0, d_unit_last, d_ws,
-                                               reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, nullptr, nlists, 1, d_start0, nullptr);
+    hipError_t e = tpf::launch_lists_unit_last(X, d_unit_last, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_unit_last");
 }
 
@@ -650,9 +667,9 @@ int tpf_p4ndec256v32_lists_units(const uint8_t * d_in, uint64_t in_bytes, const 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_units(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
-                                           d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_sel, d_ufirst, d_ucount, nsel, d_out,
-                                           out_values, d_out_ptr, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_units(X, d1 != 0, d_sel, d_ufirst, d_ucount, nsel, d_out, out_values, d_out_ptr, d_ws,
+                                           reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_units");
 }
 
@@ -679,9 +696,9 @@ int tpf_lists_intersect(const uint8_t * d_in, uint64_t in_bytes, const uint64_t 
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // d_err is reset by the launcher, together with its workspace header
-    hipError_t e = tpf::launch_lists_intersect(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last,
-                                               d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr,
-                                               d_out_pidx, d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_intersect(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
+                                               d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_intersect");
 }
 
@@ -710,9 +727,9 @@ int tpf_lists_union(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // d_err is reset by the launcher, together with its workspace header
-    hipError_t e = tpf::launch_lists_union(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last, d_probe,
-                                           probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx, d_out_tpos,
-                                           d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_union(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
+                                           d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_union");
 }
 
@@ -739,9 +756,9 @@ int tpf_lists_difference(const uint8_t * d_in, uint64_t in_bytes, const uint64_t
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // d_err is reset by the launcher, together with its workspace header
-    hipError_t e = tpf::launch_lists_difference(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last,
-                                                d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr,
-                                                d_out_pidx, d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_difference(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
+                                                d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_difference");
 }
 
@@ -769,9 +786,9 @@ int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // d_err is reset by the launcher, together with its workspace header
-    hipError_t e = tpf::launch_lists_gather(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
-                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_pos, pos_values, d_pos_ptr, d_qlist,
-                                            nq, d_out, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_gather(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nq, d_out, d_ws,
+                                            reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_gather");
 }
 
@@ -820,10 +837,10 @@ int tpf_lists_append(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_append(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
-                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_add, add_values, d_add_ptr,
-                                            nlists_out, d_out, out_cap, d_off_out, units_cap, d_list_ptr_out, d_list_unit_out,
-                                            d1 ? d_unit_last_out : nullptr, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_append(X, d1 != 0, d_add, add_values, d_add_ptr, nlists_out, d_out, out_cap, d_off_out, units_cap,
+                                            d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
+                                            reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_append");
 }
 
@@ -871,10 +888,9 @@ int tpf_lists_remove(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = prep_err(d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_remove(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1 != 0,
-                                            d1 ? d_start0 : nullptr, d1 ? d_unit_last : nullptr, d_pos, pos_values, d_pos_ptr, d_qlist,
-                                            nlists ? nq : 0u, stage_values, d_out, out_cap, d_off_out, units_cap, d_list_ptr_out,
-                                            d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
+    hipError_t e = tpf::launch_lists_remove(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nlists ? nq : 0u, stage_values, d_out, out_cap,
+                                            d_off_out, units_cap, d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
                                             reinterpret_cast<unsigned long long *>(d_err), s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_remove");
 }

@@ -159,19 +159,19 @@ hipError_t launch_d1chain_sums(const uint8_t * in, uint64_t in_bytes, const uint
 
 // Phase A over a lists stream (p4_lists.hip): the chained decode's workspace
 // layout and run scan, tails skipped through the unit records.
-hipError_t launch_lists_sums(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint32_t * rec,
-                             const dev::ListsHdr * hdr, uint64_t nlists, void * ws, ChainView * view, unsigned long long * err,
-                             hipStream_t stream)
+hipError_t launch_lists_sums(const ListsIndex & X, const uint32_t * rec, const dev::ListsHdr * hdr, void * ws, ChainView * view,
+                             unsigned long long * err, hipStream_t stream)
 {
+    const uint64_t nunits = X.nunits;
     const ChainWs<uint32_t> w = ChainWs<uint32_t>::carve(ws, nunits);
     const RunScanWs<uint32_t> & rs = w.scan;
-    dev::DecArgs A{in, in_bytes, off, nunits, nullptr, nullptr, 0u, w.sums, err};
+    dev::DecArgs A{X.in, X.in_bytes, X.off, nunits, nullptr, nullptr, 0u, w.sums, err};
     A.run_tot = rs.tot;
     *view = ChainView{w.sums, rs.pre, rs.tile};
     constexpr uint64_t per_wg = 4ull * dev::kSumRun;
     const uint64_t wgs = std::min<uint64_t>((nunits + per_wg - 1) / per_wg, grid_cap(stream, kDsumWgPerCu));
     hipLaunchKernelGGL((dev::k_dsum256v32_lists<kDsumWindow>), dim3(static_cast<uint32_t>(wgs)), dim3(256), 0, stream, A,
-                       dev::DsumLists{rec, hdr, nlists});
+                       dev::DsumLists{rec, hdr, X.nlists});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return e;

@@ -9,13 +9,37 @@
 // -> decode (k_lists_dec).  Nothing comes back to the host in between: every
 // kernel after the plan reads the header below and does nothing when the list
 // structure was refused.  The device helpers the lists kernels share are in
-// p4_lists_dev.h, the host ones (workspace carver, grids) in p4_lists_host.h.
+// p4_lists_dev.h (the tails driver among them) and p4_lists_items.h (the item
+// drivers), the host ones (grids, the launch helpers) in p4_lists_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tpf_ws.h"
+
+namespace tpf
+{
+
+// A resident index as the entry points are handed it: the stream and its unit
+// offsets, the lists' CSR pointers, the unit directory (tpf_lists_unit_base)
+// and, for a delta-1 stream, the lists' starts and the skip table
+// (tpf_lists_unit_last; values, never indices).  An entry that does not take a
+// member leaves it null; a plain stream has neither start0 nor unit_last.
+struct ListsIndex
+{
+    const uint8_t * in;
+    uint64_t in_bytes;
+    const uint64_t * off;
+    uint64_t nunits;
+    const uint64_t * ptr;
+    const uint32_t * list_unit;
+    uint64_t nlists;
+    const uint32_t * start0;
+    const uint32_t * unit_last;
+};
+
+} // namespace tpf
 
 namespace tpf::dev
 {
@@ -83,25 +107,25 @@ constexpr uint32_t kItemNone = 0xFFFFFFFFu; // unit word / list word: the reques
 constexpr uint32_t kIxQ = 0x1FFu;
 constexpr uint32_t kIxFound = 0x200u;
 
+// What the item drivers read (p4_lists_items.h): the index, the request's plan
+// and the items.  IxArgs and GaArgs embed it.
+struct ItemArgs
+{
+    ListsIndex ix;
+    const ItemHdr * hdr;
+    const uint32_t * pu;    // per request index: source unit | kRecTail, or kItemNone
+    const uint32_t * pl;    // per request index: target list, or kItemNone
+    const uint32_t * ihead; // per item: its first request index ...
+    const uint32_t * iend;  // ... and one past its last
+    unsigned long long * err;
+};
+
 struct IxArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * ptr;
-    const uint32_t * list_unit;
-    const uint32_t * start0;
-    const uint32_t * unit_last; // the skip table (values, never indices)
+    ItemArgs it;            // hdr->spare: the entry's own total
     const uint32_t * probe;
-    uint64_t pv;                // probe_values
-    const ItemHdr * hdr;        // spare: the entry's own total
-    const uint32_t * pu;        // per probe value: source unit | kRecTail, or kItemNone
-    const uint32_t * pl;        // per probe value: target list, or kItemNone
-    const uint32_t * ihead;     // per item: its first probe index ...
-    const uint32_t * iend;      // ... and one past its last
-    uint32_t * res;             // per probe value: the result word (above)
-    unsigned long long * err;
+    uint64_t pv;            // probe_values
+    uint32_t * res;         // per probe value: the result word (above)
 };
 
 } // namespace tpf::dev
@@ -135,9 +159,8 @@ struct ListsEncPlanView
 ListsEncPlanView lists_enc_plan_view(void * ws, uint64_t units_cap, uint64_t nlists);
 hipError_t launch_lists_enc_planned(const uint32_t * in, const uint64_t * ptr, uint64_t nlists, bool d1, const uint32_t * start0,
                                     uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t units_cap, void * ws, hipStream_t s);
-hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                            uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
-                            unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_dec(const ListsIndex & X, bool d1, uint32_t * out, uint64_t out_values, void * ws, unsigned long long * err,
+                            hipStream_t s);
 // the read side of a resident index (p4_lists_select.hip): the
 // unit directory of a stream, and the decode of a selection of its lists.
 // Passes of the selective decode: plan over the SELECTION -> two run scans
@@ -150,10 +173,8 @@ hipError_t launch_lists_unit_base(const uint64_t * ptr, uint64_t nlists, uint32_
                                   hipStream_t s);
 uint64_t lists_select_unit_cap(uint64_t nsel, uint64_t out_values);
 size_t lists_select_workspace(uint64_t nsel, uint64_t out_values);
-hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
-                               uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
-                               hipStream_t s);
+hipError_t launch_lists_select(const ListsIndex & X, bool d1, const uint32_t * sel, uint64_t nsel, uint32_t * out, uint64_t out_values,
+                               uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s);
 // block-range reads of a resident index (p4_lists_units.hip):
 // the skip table of a delta-1 stream (the last value of every unit), the
 // search from doc-id ranges to unit ranges, and the decode of unit ranges of
@@ -162,9 +183,7 @@ hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint
 // decode: plan over the SELECTION -> two run scans -> heads -> full blocks ->
 // tails, the same for delta-1 (a unit starts from the table) and plain.
 size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists);
-hipError_t launch_lists_unit_last(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                  uint64_t nlists, const uint32_t * start0, uint32_t * unit_last, void * ws, unsigned long long * err,
-                                  hipStream_t s);
+hipError_t launch_lists_unit_last(const ListsIndex & X, uint32_t * unit_last, void * ws, unsigned long long * err, hipStream_t s);
 // the passes the selective decode and the units decode share after their plan
 // kernels (p4_lists_select.hip): the two run scans (hdr->vtotal, hdr->ototal)
 // and the heads (the verdict, d_out_ptr, vbase, the virtual units' records)
@@ -175,10 +194,9 @@ hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t *
                                     const uint32_t * qlist, const uint32_t * qlo, const uint32_t * qhi, uint64_t nq, uint32_t * ufirst,
                                     uint32_t * ucount, unsigned long long * err, hipStream_t s);
 size_t lists_units_workspace(uint64_t nsel, uint64_t out_values);
-hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                              const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                              const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount, uint64_t nsel, uint32_t * out,
-                              uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_units(const ListsIndex & X, bool d1, const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount,
+                              uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
+                              hipStream_t s);
 // membership of probe values in resident lists (p4_lists_intersect.hip;
 // DESIGN.md 4.11).  Passes: plan (one thread per query: the checks; one per
 // probe value: its query, then its unit by a search over the skip table) ->
@@ -187,16 +205,13 @@ hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint6
 // searched, never stored) -> hit flags and their run scan -> compaction
 // (d_out_ptr, the verdict, the scatter).  Sized by nq and probe_values alone.
 size_t lists_intersect_workspace(uint64_t nq, uint64_t probe_values);
-hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                  const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                                  const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
-                                  uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
-                                  uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_intersect(const ListsIndex & X, const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr,
+                                  const uint32_t * qlist, uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr,
+                                  uint32_t * out_pidx, uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // the intersection's plan and its lookup (full blocks, tails) for other entries: `every` runs the EVERY
 // form of the lookup (dev::kIxFound above); pu / pl / ihead / iend / res as the item layer below leaves them
-hipError_t launch_ix_plan(const uint64_t * ptr, const uint32_t * list_unit, uint64_t nlists, uint64_t nunits, const uint32_t * unit_last,
-                          const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
-                          dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s);
+hipError_t launch_ix_plan(const ListsIndex & X, const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist,
+                          uint64_t nq, dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s);
 hipError_t launch_ix_lookup(const dev::IxArgs & A, bool every, hipStream_t s);
 // the item layer the intersection and the gather share (p4_lists_items.hip).  pu / pl: per request index
 // its source unit | kRecTail and its list, or kItemNone (the entry's plan).
@@ -215,9 +230,7 @@ hipError_t launch_items(uint64_t pv, dev::ItemHdr * hdr, const uint32_t * pu, co
 // out[i] = vals[pos[i] % 256]; the tails kernel also writes the verdict of a
 // refusal).  Sized by pos_values alone.
 size_t lists_gather_workspace(uint64_t nq, uint64_t pos_values);
-hipError_t launch_lists_gather(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0,
-                               const uint32_t * unit_last, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
+hipError_t launch_lists_gather(const ListsIndex & X, bool d1, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
                                const uint32_t * qlist, uint64_t nq, uint32_t * out, void * ws, unsigned long long * err, hipStream_t s);
 // the sorted union of probe values with resident lists (p4_lists_union.hip;
 // DESIGN.md 4.16).  Passes: the intersection's plan, items and lookup (EVERY:
@@ -228,11 +241,9 @@ hipError_t launch_lists_gather(const uint8_t * in, uint64_t in_bytes, const uint
 // list value shifted by the misses at or before it) -> the hits' pidx.  Sized
 // by nq, probe_values and out_values alone.
 size_t lists_union_workspace(uint64_t nq, uint64_t probe_values, uint64_t out_values);
-hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                              const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                              const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
-                              uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
-                              uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_union(const ListsIndex & X, const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr,
+                              const uint32_t * qlist, uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr,
+                              uint32_t * out_pidx, uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // the probe values that are NOT in resident lists (p4_lists_difference.hip;
 // DESIGN.md 4.17).  Passes: the intersection's plan, items and lookup (EVERY:
 // q and the member flag of every probe value that has a unit) -> miss flags
@@ -240,11 +251,9 @@ hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint6
 // compaction (d_out_ptr, the verdict, the scatter of value, probe index and
 // L).  Sized by probe_values alone, as the intersection.
 size_t lists_difference_workspace(uint64_t nq, uint64_t probe_values);
-hipError_t launch_lists_difference(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                   const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                                   const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr, const uint32_t * qlist,
-                                   uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx,
-                                   uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_difference(const ListsIndex & X, const uint32_t * probe, uint64_t probe_values, const uint64_t * probe_ptr,
+                                   const uint32_t * qlist, uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr,
+                                   uint32_t * out_pidx, uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s);
 // postings appended to the lists of a resident index (p4_lists_append.hip;
 // DESIGN.md 4.13).  Passes: plan (one thread per output list: the checks, what
 // of its old tail is staged, its new units) -> four run scans -> heads (the
@@ -254,11 +263,9 @@ hipError_t launch_lists_difference(const uint8_t * in, uint64_t in_bytes, const 
 // d_unit_last_out) -> stitch (a wave per kListsAppendTile bytes of d_out).
 // Sized by nunits, nlists_out and add_values alone.
 size_t lists_append_workspace(uint64_t nunits, uint64_t nlists_out, uint64_t add_values);
-hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
-                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                               const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t nlists_out, uint8_t * out,
-                               uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out,
-                               uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s);
+hipError_t launch_lists_append(ListsIndex X, bool d1, const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t nlists_out,
+                               uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out,
+                               uint32_t * lunit_out, uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s);
 // postings deleted at list positions of a resident index (p4_lists_remove.hip;
 // DESIGN.md 4.18).  Passes: plan over the QUERIES (the checks, the unit range
 // [u0, end) of every targeted list, its compacted count) and over the positions
@@ -269,12 +276,10 @@ hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint
 // (p4_lists_stitch.h), the last three as the append's.  Workspace, decode and
 // encoder are sized by nq and stage_values, the per-list arrays by nlists.
 size_t lists_remove_workspace(uint64_t nlists, uint64_t nq, uint64_t stage_values);
-hipError_t launch_lists_remove(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
-                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                               const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr, const uint32_t * qlist, uint64_t nq,
-                               uint64_t stage_values, uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap,
-                               uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out, void * ws, unsigned long long * err,
-                               hipStream_t s);
+hipError_t launch_lists_remove(const ListsIndex & X, bool d1, const uint32_t * pos, uint64_t pos_values, const uint64_t * pos_ptr,
+                               const uint32_t * qlist, uint64_t nq, uint64_t stage_values, uint8_t * out, uint64_t out_cap,
+                               uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out,
+                               void * ws, unsigned long long * err, hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them
@@ -282,8 +287,7 @@ struct ChainView
 {
     const uint32_t *sums = nullptr, *pre = nullptr, *tile = nullptr;
 };
-hipError_t launch_lists_sums(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint32_t * rec,
-                             const dev::ListsHdr * hdr, uint64_t nlists, void * ws, ChainView * view, unsigned long long * err,
-                             hipStream_t stream);
+hipError_t launch_lists_sums(const ListsIndex & X, const uint32_t * rec, const dev::ListsHdr * hdr, void * ws, ChainView * view,
+                             unsigned long long * err, hipStream_t stream);
 
 } // namespace tpf

@@ -14,13 +14,7 @@ namespace tpf::dev
 
 struct ListsArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * ptr;
-    uint64_t nlists;
-    const uint32_t * start0;
+    ListsIndex ix;             // (no unit directory and no skip table: the decode of a whole stream builds its own)
     uint32_t * out;
     const ListsHdr * hdr;
     const uint32_t * rec;      // unit records (p4_lists.h)
@@ -125,13 +119,14 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
 {
     __shared__ uint32_t slots[4][kSlotBytes / 4];
     __shared__ uint32_t scratch[4][kWaveScratchU32];
-    if (!lists_go(A.hdr, A.nunits))
+    const ListsIndex & X = A.ix;
+    if (!lists_go(A.hdr, X.nunits))
         return;
     constexpr uint32_t kRun = kRunDefault;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, A.nunits);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRun, X.nunits);
     const uint32_t t = R.t;
     const uint64_t first = R.first;
-    if (first >= A.nunits)
+    if (first >= X.nunits)
         return;
     uint32_t * slot = slots[R.wv];
     uint32_t * scr = scratch[R.wv];
@@ -142,8 +137,8 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
     const uint64_t fullmask = __ballot(full);
     if (fullmask == 0ull)
         return; // a run of tails only
-    const uint64_t o = full ? A.off[u] : 0ull;
-    const uint64_t e = full ? A.off[u + 1u] : 0ull;
+    const uint64_t o = full ? X.off[u] : 0ull;
+    const uint64_t e = full ? X.off[u + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
     P.init(R.in_base, R.in_end, o, e, full);
     // the first NC - 1 units' bytes go in flight before the list plane's
@@ -152,17 +147,10 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
     Chunk C[NC];
     pipe_prime<NC>(P, C, t);
 
-    // ---- the list of every unit: heads inside the run, the search before it
-    const uint32_t r0 = rl(r, 0) & kRecList;
-    const uint32_t j0 = r0 != 0u ? r0 - 1u : find_list(A.ubase, static_cast<uint32_t>(A.nlists), static_cast<uint32_t>(first), t);
-    const uint32_t id = umax32(wave_incl_max(r & kRecList), j0 + 1u) - 1u;
+    const uint32_t id = run_ids(r, A.ubase, X.nlists, first, t); // the list of every unit
     const uint32_t ub = valid ? A.ubase[id] : 0u;
-    const uint64_t p0 = valid ? A.ptr[id] : 0ull;
-    const uint64_t opos = p0 + 256ull * (static_cast<uint32_t>(u) - ub); // unit u - ub of its list
-    const uint64_t opos0 = readlane_u64(opos, 0);
-    const uint32_t rel = static_cast<uint32_t>(opos - opos0) * 4u; // bytes from the run's first value
-    const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(A.out + opos0, rl(rel, lastf) + 1024u);
+    const uint64_t p0 = valid ? X.ptr[id] : 0ull;
+    const RunOut O(A.out, p0 + 256ull * (static_cast<uint32_t>(u) - ub), fullmask); // unit u - ub of its list
 
     uint32_t startv = 0u;
     if constexpr (D1)
@@ -173,11 +161,11 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
         static_assert(kSumRun % kRun == 0u, "decode runs nest in phase A's runs");
         const uint64_t f = first / kSumRun * kSumRun;
         const uint32_t kk = static_cast<uint32_t>(first - f);
-        const uint32_t sv = f + t < A.nunits ? A.sums[f + t] : 0u;
+        const uint32_t sv = f + t < X.nunits ? A.sums[f + t] : 0u;
         const uint32_t ex = wave_incl_scan(sv) - sv;
         const uint32_t pu = run_base(A.run_pre, A.run_tile, first / kSumRun)
                             + static_cast<uint32_t>(__shfl(static_cast<int>(ex), static_cast<int>((kk + t) & 63u), 64));
-        const uint32_t s0 = (valid && A.start0 != nullptr) ? A.start0[id] : 0u;
+        const uint32_t s0 = (valid && X.start0 != nullptr) ? X.start0[id] : 0u;
         startv = valid ? s0 + pu - A.pbase[id] : 0u;
     }
 
@@ -187,14 +175,14 @@ __global__ __launch_bounds__(256, MINW) void k_lists_dec(const ListsArgs A)
             return;
         u32x4 v;
         decode_full_unit<D1>(P, c, jj, slot, scr, rl(startv, jj), t, v, badmask);
-        st16_run(ors, rl(rel, jj) + 16u * t, v);
+        O.store(jj, t, v);
         wave_lds_sync();
     });
     report_bad_units(A.err, badmask, static_cast<uint32_t>(u), t);
 }
 
-// Decode of the tails: every wave owns kRunDefault consecutive LISTS with the
-// generic decoder's pipeline (k_dec_gr, p4_generic.hip); lane t holds list
+// Decode of the tails: every wave owns kRunDefault consecutive LISTS through
+// the tails driver (tail_units, p4_lists_dev.h); lane t holds list
 // first + t's tail unit -- unit ubase + n / 256 of n % 256 values at the end
 // of the list's output -- or nothing when the list has no tail.  Delta-1: the
 // tail starts at start0 + P(ubase[j + 1]) - P(ubase[j]), every full block of
@@ -206,47 +194,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_li
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
     __shared__ uint32_t scratch[4][kListScratchU32];
-    if (!lists_go(A.hdr, A.nunits))
+    const ListsIndex & X = A.ix;
+    if (!lists_go(A.hdr, X.nunits))
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRunDefault, X.nlists);
     const uint32_t t = R.t;
-    if (R.first >= A.nlists)
+    if (R.first >= X.nlists)
         return;
-    uint32_t * slot = slots[R.wv];
     const uint64_t j = R.first + t;
-    const uint64_t p0 = t < R.n ? A.ptr[j] : 0ull;
-    const uint64_t p1 = t < R.n ? A.ptr[j + 1u] : 0ull;
+    const uint64_t p0 = t < R.n ? X.ptr[j] : 0ull;
+    const uint64_t p1 = t < R.n ? X.ptr[j + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
     if (hasmask == 0ull)
         return;
     const uint32_t u = has ? A.ubase[j] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
-    const uint64_t o = has ? A.off[u] : 0ull;
-    const uint64_t e = has ? A.off[u + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
     const uint64_t opos = p1 - cnt;
-    uint32_t startv = 0u;
-    if constexpr (D1)
-        startv = has ? (A.start0 != nullptr ? A.start0[j] : 0u) + A.pbase[j + 1u] - A.pbase[j] : 0u;
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals v;
-        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, v, badmask);
-        uint32_t * op = A.out + readlane_u64(opos, jj);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            if (t + 64u * q < cj)
-                __builtin_nontemporal_store(v.v[q], op + t + 64u * q);
-        wave_lds_sync();
-    });
-    report_bad_units(A.err, badmask, u, t);
+    tail_units<D1, NC>(
+        R, X.off, has, hasmask, u, cnt, slots[R.wv], scratch[R.wv], A.err,
+        [&] { return D1 && has ? (X.start0 != nullptr ? X.start0[j] : 0u) + A.pbase[j + 1u] - A.pbase[j] : 0u; },
+        tail_store<true>(A.out, opos, t));
 }
 
 } // namespace tpf::dev
@@ -290,58 +258,46 @@ hipError_t launch_lists_structure(const uint64_t * ptr, uint64_t nlists, uint64_
     hipError_t e = fill_u32(hdr, 0xFFFFFFFFu, 4, s);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_lists_plan, dim3(flat_grid(std::max(nunits, nlists), s)), dim3(256), 0, s, ptr, nlists, values, scan.tot,
-                       hdr, rec, nunits);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_lists_plan, flat_grid(std::max(nunits, nlists), s), 256, s, ptr, nlists, values, scan.tot, hdr, rec, nunits))
+        != hipSuccess)
         return e;
     if ((e = launch_run_scan_u64(scan.tot, nlists, scan.pre, scan.tile, reinterpret_cast<uint64_t *>(&hdr->total), s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_lists_heads, dim3(flat_grid(nlists, s)), dim3(256), 0, s, ptr, nlists, nunits, scan.pre, scan.tile, hdr,
-                       ubase, rec, err);
-    return hipGetLastError();
+    return launch(dev::k_lists_heads, flat_grid(nlists, s), 256, s, ptr, nlists, nunits, scan.pre, scan.tile, hdr, ubase, rec, err);
 }
 
-hipError_t launch_lists_dec(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                            uint64_t nlists, bool d1, const uint32_t * start0, uint32_t * out, uint64_t out_values, void * ws,
-                            unsigned long long * err, hipStream_t s)
+hipError_t launch_lists_dec(const ListsIndex & X, bool d1, uint32_t * out, uint64_t out_values, void * ws, unsigned long long * err,
+                            hipStream_t s)
 {
+    const uint64_t nunits = X.nunits, nlists = X.nlists;
     if (nunits == 0 || nlists == 0)
         return hipSuccess;
     if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const ListsWs W(ws, nunits, nlists);
-    hipError_t e = launch_lists_structure(ptr, nlists, out_values, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
+    hipError_t e = launch_lists_structure(X.ptr, nlists, out_values, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
     if (e != hipSuccess)
         return e;
-    dev::ListsArgs A{in, in_bytes, off, nunits, ptr, nlists, start0, out, W.hdr, W.rec, W.ubase, W.pbase,
-                     nullptr, nullptr, nullptr, err};
-    const uint32_t grid = static_cast<uint32_t>((nunits + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    const uint32_t tgrid = static_cast<uint32_t>((nlists + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    if (!d1)
+    dev::ListsArgs A{.ix = X, .out = out, .hdr = W.hdr, .rec = W.rec, .ubase = W.ubase, .pbase = W.pbase, .err = err};
+    if (d1)
     {
-        hipLaunchKernelGGL((dev::k_lists_dec<false, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
+        // phase A keeps the first parse error of a full block; the decode pass
+        // re-checks every unit (tails included) into the same word
+        ChainView cv;
+        if ((e = launch_lists_sums(X, W.rec, W.hdr, W.chain, &cv, err, s)) != hipSuccess)
             return e;
-        hipLaunchKernelGGL((dev::k_lists_tails<false, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-        return hipGetLastError();
+        A.sums = cv.sums;
+        A.run_pre = cv.pre;
+        A.run_tile = cv.tile;
+        if ((e = launch(dev::k_lists_pbase, flat_grid(nlists + 1u, s), 256, s, nlists, nunits, W.ubase, cv.sums, cv.pre, cv.tile, W.hdr, W.pbase))
+            != hipSuccess)
+            return e;
     }
-    // phase A keeps the first parse error of a full block; the decode pass
-    // re-checks every unit (tails included) into the same word
-    ChainView cv;
-    if ((e = launch_lists_sums(in, in_bytes, off, nunits, W.rec, W.hdr, nlists, W.chain, &cv, err, s)) != hipSuccess)
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_lists_dec<D1, dev::kListsNC, dev::kListsMinW>; },
+                       wave_grid(nunits, dev::kRunDefault), 256, s, A))
+        != hipSuccess)
         return e;
-    A.sums = cv.sums;
-    A.run_pre = cv.pre;
-    A.run_tile = cv.tile;
-    hipLaunchKernelGGL(dev::k_lists_pbase, dim3(flat_grid(nlists + 1u, s)), dim3(256), 0, s, nlists, nunits, W.ubase, cv.sums, cv.pre, cv.tile,
-                       W.hdr, W.pbase);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_lists_dec<true, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_lists_tails<true, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    return hipGetLastError();
+    return launch_by(d1, [](auto D1) { return dev::k_lists_tails<D1, dev::kTailsNC>; }, wave_grid(nlists, dev::kRunDefault), 256, s, A);
 }
 
 } // namespace tpf

@@ -51,15 +51,7 @@ struct AppHdr
 
 struct AppArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * lptr;
-    const uint32_t * lunit;
-    uint64_t nlists;
-    const uint32_t * start0;
-    const uint32_t * unit_last;
+    ListsIndex ix; // the old index; empty: nunits = nlists = in_bytes = 0
     const uint32_t * add;
     uint64_t add_values;
     const uint64_t * aptr;
@@ -127,13 +119,13 @@ __global__ __launch_bounds__(256) void k_app_plan(const AppArgs A)
     uint32_t tv = 0u, m = 0u, db = 0u;
     if (j < A.n)
     {
-        const bool old = j < A.nlists;
-        const uint64_t p0 = old ? A.lptr[j] : 0ull, p1 = old ? A.lptr[j + 1u] : 0ull;
+        const bool old = j < A.ix.nlists;
+        const uint64_t p0 = old ? A.ix.ptr[j] : 0ull, p1 = old ? A.ix.ptr[j + 1u] : 0ull;
         const uint64_t a0 = A.aptr[j], a1 = A.aptr[j + 1u];
         const uint64_t oldn = p1 - p0;
         const uint64_t cnt = (oldn >> 8) + ((oldn & 255u) != 0u ? 1u : 0u);
-        const uint64_t lu0 = old ? A.lunit[j] : 0u, lu1 = old ? A.lunit[j + 1u] : 0u;
-        bool bad = p1 < p0 || a1 < a0 || a1 > A.add_values || lu1 - lu0 != cnt || lu1 > A.nunits;
+        const uint64_t lu0 = old ? A.ix.list_unit[j] : 0u, lu1 = old ? A.ix.list_unit[j + 1u] : 0u;
+        bool bad = p1 < p0 || a1 < a0 || a1 > A.add_values || lu1 - lu0 != cnt || lu1 > A.ix.nunits;
         if (!bad)
         {
             const uint64_t addn = a1 - a0; // < 2^31
@@ -143,12 +135,12 @@ __global__ __launch_bounds__(256) void k_app_plan(const AppArgs A)
             if (cnt != 0u)
             {
                 // the ends of the copied range; the dropped tail's offsets
-                const uint64_t o0 = A.off[lu0], o1 = A.off[lu0 + keep];
-                bad = o0 > o1 || o1 > A.in_bytes;
+                const uint64_t o0 = A.ix.off[lu0], o1 = A.ix.off[lu0 + keep];
+                bad = o0 > o1 || o1 > A.ix.in_bytes;
                 if (!bad && tt)
                 {
-                    const uint64_t o2 = A.off[lu1];
-                    if (o2 < o1 || o2 > A.in_bytes || o2 - o1 > kAppTailMax)
+                    const uint64_t o2 = A.ix.off[lu1];
+                    if (o2 < o1 || o2 > A.ix.in_bytes || o2 - o1 > kAppTailMax)
                         atomicMin(&A.hdr->tbad, static_cast<unsigned long long>(lu1 - 1u));
                     else
                         db = static_cast<uint32_t>(o2 - o1);
@@ -194,8 +186,8 @@ __global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
             app_err(A.err, h.tbad != ~0ull ? h.tbad : A.ebase + h.bad);
         return;
     }
-    const uint64_t lu00 = A.nlists != 0u ? A.lunit[0] : 0u;
-    const uint64_t luN = A.nlists != 0u ? A.lunit[A.nlists] : 0u;
+    const uint64_t lu00 = A.ix.nlists != 0u ? A.ix.list_unit[0] : 0u;
+    const uint64_t luN = A.ix.nlists != 0u ? A.ix.list_unit[A.ix.nlists] : 0u;
     const uint64_t nuo = (luN - lu00) - h.tt + h.m;
     const bool ufit = nuo <= A.units_cap && nuo <= 0x7FFFFFFFull;
     const bool in = j < A.n;
@@ -217,9 +209,9 @@ __global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
     {
         TV = h.tv, TT = h.tt, M = h.m, DB = h.db;
     }
-    const uint64_t jo = j < A.nlists ? j : A.nlists; // lists past the old index are empty there
-    const uint64_t lu = A.nlists != 0u ? A.lunit[jo] : 0u;
-    const uint64_t oldoff = A.nlists != 0u ? A.lptr[jo] - A.lptr[0] : 0ull;
+    const uint64_t jo = j < A.ix.nlists ? j : A.ix.nlists; // lists past the old index are empty there
+    const uint64_t lu = A.ix.nlists != 0u ? A.ix.list_unit[jo] : 0u;
+    const uint64_t oldoff = A.ix.nlists != 0u ? A.ix.ptr[jo] - A.ix.ptr[0] : 0ull;
     const uint64_t a0 = A.aptr[j];
     const uint64_t addoff = a0 - A.aptr[0];
     A.lptr_out[j] = oldoff + addoff;
@@ -232,7 +224,7 @@ __global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
     }
     A.sptr[j] = addoff + TV;
     A.subase[j] = static_cast<uint32_t>(M);
-    A.kbpre[j] = (A.nunits != 0u && A.nlists != 0u ? A.off[lu] - A.off[lu00] : 0ull) - DB;
+    A.kbpre[j] = (A.ix.nunits != 0u && A.ix.nlists != 0u ? A.ix.off[lu] - A.ix.off[lu00] : 0ull) - DB;
     if (in)
     {
         const uint64_t addn = A.aptr[j + 1u] - a0;
@@ -248,8 +240,8 @@ __global__ __launch_bounds__(256) void k_app_heads(const AppArgs A)
         if constexpr (D1)
         {
             // the staged values continue the list: from the last kept full block, or from start0
-            const uint64_t oldn = j < A.nlists ? A.lptr[j + 1u] - A.lptr[j] : 0ull;
-            A.sst[j] = oldn < 256u ? (A.start0 != nullptr ? A.start0[j] : 0u) : A.unit_last[lu + (oldn >> 8) - 1u];
+            const uint64_t oldn = j < A.ix.nlists ? A.ix.ptr[j + 1u] - A.ix.ptr[j] : 0ull;
+            A.sst[j] = oldn < 256u ? (A.ix.start0 != nullptr ? A.ix.start0[j] : 0u) : A.ix.unit_last[lu + (oldn >> 8) - 1u];
         }
     }
     else
@@ -283,9 +275,10 @@ __global__ __launch_bounds__(256) void k_app_stage_add(const AppArgs A)
 }
 
 // ---- stage: the old tails -----------------------------------------------------
-// k_un_tails's shape (p4_lists_units.hip): every wave owns kRunDefault
-// consecutive lists with the generic decoder's pipeline; lane t holds list
-// first + t's old tail -- the list's last unit, tv values -- or nothing.
+// Every wave owns kRunDefault consecutive lists through the tails driver
+// (tail_units, p4_lists_dev.h); lane t holds list first + t's old tail -- the
+// list's last unit, tv values -- or nothing.  The staged values are read again
+// at once by the encoder's passes: they are stored plainly.
 template <bool D1, uint32_t NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_app_stage_tails(const AppArgs A)
 {
@@ -293,46 +286,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ap
     __shared__ uint32_t scratch[4][kListScratchU32];
     if (A.hdr->go == 0u)
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const WaveRun R = wave_run(A.ix.in, A.ix.in_bytes, kRunDefault, A.ix.nlists);
     const uint32_t t = R.t;
-    if (R.first >= A.nlists)
+    if (R.first >= A.ix.nlists)
         return;
-    uint32_t * slot = slots[R.wv];
     const uint64_t k = R.first + t;
     const uint32_t cnt = t < R.n ? A.tv[k] : 0u;
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
     if (hasmask == 0ull)
         return;
-    const uint32_t su = has ? A.lunit[k + 1u] - 1u : 0u; // the list's last unit
-    const uint64_t o = has ? A.off[su] : 0ull;
-    const uint64_t e = has ? A.off[su + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
-    const uint64_t opos = has ? A.sptr[k] : 0ull;
-    uint32_t startv = 0u;
-    if constexpr (D1)
-    {
-        if (has)
-            startv = A.sst[k];
-    }
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals x;
-        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
-        uint32_t * op = A.stage + readlane_u64(opos, jj);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            if (t + 64u * q < cj)
-                op[t + 64u * q] = x.v[q];
-        wave_lds_sync();
-    });
-    report_bad_units(A.err, badmask, su, t);
+    const uint32_t su = has ? A.ix.list_unit[k + 1u] - 1u : 0u; // the list's last unit
+    uint64_t opos = 0ull;
+    tail_units<D1, NC>(
+        R, A.ix.off, has, hasmask, su, cnt, slots[R.wv], scratch[R.wv], A.err,
+        [&] {
+            // where the staged list begins, gathered behind the offsets' loads
+            opos = has ? A.sptr[k] : 0ull;
+            return D1 && has ? A.sst[k] : 0u;
+        },
+        tail_store<false>(A.stage, opos, t));
 }
 
 // ---- segs: where every list's bytes start, and the capacity -----------------------
@@ -372,14 +345,14 @@ __global__ __launch_bounds__(256) void k_app_offsets(const AppArgs A)
         return;
     const uint64_t j = gallop(A.lunit_out, static_cast<uint32_t>(A.n), j0, u);
     const uint32_t local = static_cast<uint32_t>(u) - A.lunit_out[j];
-    const bool old = j < A.nlists;
-    const uint32_t lu = old ? A.lunit[j] : 0u;
-    const uint32_t keep = old ? A.lunit[j + 1u] - lu - (A.tv[j] != 0u ? 1u : 0u) : 0u;
+    const bool old = j < A.ix.nlists;
+    const uint32_t lu = old ? A.ix.list_unit[j] : 0u;
+    const uint32_t keep = old ? A.ix.list_unit[j + 1u] - lu - (A.tv[j] != 0u ? 1u : 0u) : 0u;
     if (local < keep)
     {
-        A.off_out[u] = A.lstart[j] + (A.off[lu + local] - A.off[lu]);
+        A.off_out[u] = A.lstart[j] + (A.ix.off[lu + local] - A.ix.off[lu]);
         if constexpr (D1)
-            A.ulast_out[u] = A.unit_last[lu + local];
+            A.ulast_out[u] = A.ix.unit_last[lu + local];
     }
     else
     {
@@ -391,7 +364,7 @@ __global__ __launch_bounds__(256) void k_app_offsets(const AppArgs A)
 }
 
 // ---- stitch -------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_app_stitch(const AppArgs A) { stitch_tile(A); }
+__global__ __launch_bounds__(256) void k_app_stitch(const AppArgs A) { stitch_tile(A, A.n); }
 
 } // namespace tpf::dev
 
@@ -461,36 +434,64 @@ size_t lists_append_workspace(uint64_t nunits, uint64_t nlists_out, uint64_t add
 // Launches, fixed by the sizes: reset, plan, 4 x 2 run scans, heads, [stage
 // additions, stage tails,] 6 of the encoder, segs, [offsets,] [stitch] -- 22
 // at the most, 23 with d_err's reset by the entry point.
-hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
-                               const uint32_t * lunit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                               const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t n, uint8_t * out,
-                               uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out,
-                               uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s)
+hipError_t launch_lists_append(ListsIndex X, bool d1, const uint32_t * add, uint64_t add_values, const uint64_t * aptr, uint64_t n,
+                               uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out,
+                               uint32_t * lunit_out, uint32_t * ulast_out, void * ws, unsigned long long * err, hipStream_t s)
 {
     hipError_t e;
-    const uint64_t ebase = nunits;
+    const uint64_t ebase = X.nunits;
     if (n == 0)
-    {
-        hipLaunchKernelGGL(dev::k_app_empty, dim3(1), dim3(64), 0, s, lptr_out, lunit_out, off_out);
-        return hipGetLastError();
-    }
-    if (nunits == 0 || nlists == 0) // an empty old index
-        nunits = 0, nlists = 0, in_bytes = 0;
-    const AppCaps C(nunits, n, add_values);
+        return launch(dev::k_app_empty, 1, 64, s, lptr_out, lunit_out, off_out);
+    if (X.nunits == 0 || X.nlists == 0) // an empty old index
+        X.nunits = 0, X.nlists = 0, X.in_bytes = 0;
+    const AppCaps C(X.nunits, n, add_values);
     const AppWs W(ws, n, C);
     const ListsEncPlanView V = lists_enc_plan_view(W.enc, C.units, n);
-    const dev::AppArgs A{in,        in_bytes,  off,        nunits,    lptr,      lunit,     nlists,     start0,    unit_last,
-                         add,       add_values, aptr,      n,         out,       out_cap,   off_out,    units_cap, lptr_out,
-                         lunit_out, ulast_out, err,        W.hdr,     W.stv.tot, W.stt.tot, W.sm.tot,   W.sdb.tot, W.stv.pre,
-                         W.stv.tile, W.stt.pre, W.stt.tile, W.sm.pre, W.sm.tile, W.sdb.pre, W.sdb.tile, W.tv,      W.m,
-                         W.db,      W.sst,     W.sptr,     W.kbpre,   W.lstart,  W.stage,   W.noff,     W.sbytes,  V.hdr,
-                         V.ubase,   V.rec,     C.units,   ebase};
+    const dev::AppArgs A{.ix = X,
+                         .add = add,
+                         .add_values = add_values,
+                         .aptr = aptr,
+                         .n = n,
+                         .out = out,
+                         .out_cap = out_cap,
+                         .off_out = off_out,
+                         .units_cap = units_cap,
+                         .lptr_out = lptr_out,
+                         .lunit_out = lunit_out,
+                         .ulast_out = ulast_out,
+                         .err = err,
+                         .hdr = W.hdr,
+                         .tv_tot = W.stv.tot,
+                         .tt_tot = W.stt.tot,
+                         .m_tot = W.sm.tot,
+                         .db_tot = W.sdb.tot,
+                         .tv_pre = W.stv.pre,
+                         .tv_tile = W.stv.tile,
+                         .tt_pre = W.stt.pre,
+                         .tt_tile = W.stt.tile,
+                         .m_pre = W.sm.pre,
+                         .m_tile = W.sm.tile,
+                         .db_pre = W.sdb.pre,
+                         .db_tile = W.sdb.tile,
+                         .tv = W.tv,
+                         .m = W.m,
+                         .db = W.db,
+                         .sst = W.sst,
+                         .sptr = W.sptr,
+                         .kbpre = W.kbpre,
+                         .lstart = W.lstart,
+                         .stage = W.stage,
+                         .noff = W.noff,
+                         .sbytes = W.sbytes,
+                         .ehdr = V.hdr,
+                         .subase = V.ubase,
+                         .rec = V.rec,
+                         .su_cap = C.units,
+                         .ebase = ebase};
     auto grid = [](uint64_t items, uint64_t per) { return dim3(static_cast<uint32_t>((items + per - 1u) / per)); };
-    hipLaunchKernelGGL(dev::k_app_reset, dim3(1), dim3(64), 0, s, W.hdr, V.hdr);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_app_reset, 1, 64, s, W.hdr, V.hdr)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_app_plan, grid(n, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_app_plan, grid(n, 256), 256, s, A)) != hipSuccess)
         return e;
     const uint64_t nr = app_runs(n);
     using u64p = uint64_t *;
@@ -499,51 +500,28 @@ hipError_t launch_lists_append(const uint8_t * in, uint64_t in_bytes, const uint
         || (e = launch_run_scan_u64(W.sm.tot, nr, W.sm.pre, W.sm.tile, u64p(&W.hdr->m), s)) != hipSuccess
         || (e = launch_run_scan_u64(W.sdb.tot, nr, W.sdb.pre, W.sdb.tile, u64p(&W.hdr->db), s)) != hipSuccess)
         return e;
-    if (d1)
-        hipLaunchKernelGGL(dev::k_app_heads<true>, grid(n + 1u, 256), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL(dev::k_app_heads<false>, grid(n + 1u, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_app_heads<D1>; }, grid(n + 1u, 256), 256, s, A)) != hipSuccess)
         return e;
     if (add_values != 0u)
     {
-        hipLaunchKernelGGL(dev::k_app_stage_add, grid(add_values, 256), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
+        if ((e = launch(dev::k_app_stage_add, grid(add_values, 256), 256, s, A)) != hipSuccess)
             return e;
-        if (nlists != 0u)
-        {
-            const dim3 tg = grid(nlists, 4u * dev::kRunDefault);
-            if (d1)
-                hipLaunchKernelGGL((dev::k_app_stage_tails<true, dev::kTailsNC>), tg, dim3(256), 0, s, A);
-            else
-                hipLaunchKernelGGL((dev::k_app_stage_tails<false, dev::kTailsNC>), tg, dim3(256), 0, s, A);
-            if ((e = hipGetLastError()) != hipSuccess)
-                return e;
-        }
+        if (X.nlists != 0u
+            && (e = launch_by(d1, [](auto D1) { return dev::k_app_stage_tails<D1, dev::kTailsNC>; }, grid(X.nlists, 4u * dev::kRunDefault), 256,
+                              s, A))
+                   != hipSuccess)
+            return e;
     }
     if ((e = launch_lists_enc_planned(W.stage, W.sptr, n, d1, d1 ? W.sst : nullptr, W.sbytes, C.bytes, W.noff, C.units, W.enc, s))
         != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_app_segs, grid(n + 1u, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_app_segs, grid(n + 1u, 256), 256, s, A)) != hipSuccess)
         return e;
-    if (units_cap != 0u)
-    {
-        if (d1)
-            hipLaunchKernelGGL(dev::k_app_offsets<true>, grid(units_cap, 256), dim3(256), 0, s, A);
-        else
-            hipLaunchKernelGGL(dev::k_app_offsets<false>, grid(units_cap, 256), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
-            return e;
-    }
+    if (units_cap != 0u && (e = launch_by(d1, [](auto D1) { return dev::k_app_offsets<D1>; }, grid(units_cap, 256), 256, s, A)) != hipSuccess)
+        return e;
     // the stream is never longer than the old bytes plus the staged ones
-    const uint64_t span = std::min(out_cap, in_bytes + C.bytes);
-    if (span != 0u)
-    {
-        hipLaunchKernelGGL(dev::k_app_stitch, grid(span, 4u * dev::kListsAppendTile), dim3(256), 0, s, A);
-        e = hipGetLastError();
-    }
-    return e;
+    const uint64_t span = std::min(out_cap, X.in_bytes + C.bytes);
+    return span != 0u ? launch(dev::k_app_stitch, grid(span, 4u * dev::kListsAppendTile), 256, s, A) : hipSuccess;
 }
 
 } // namespace tpf

@@ -1,10 +1,12 @@
 // p4_lists_dev.h -- device helpers shared by the lists kernels (p4_lists*.hip):
-// the pipeline shapes, a wave's run of units / lists / items, the decode of one
-// full 256v32 unit and of one p4Enc32 tail unit out of the run plane's pipeline
-// (p4_dec_run.h), the error report of a run, the checks of a list against the
-// unit directory, and how every lane of a wave's run of units finds its list
-// from the unit records (p4_lists.h).  Device code only: included by *.hip
-// files (internal).
+// the pipeline shapes, a wave's run of units / lists / items, how every lane
+// of a wave's run of units finds its list from the unit records (run_ids,
+// p4_lists.h) and where the run's blocks go (RunOut), the decode of one full
+// 256v32 unit and of one p4Enc32 tail unit out of the run plane's pipeline
+// (p4_dec_run.h), the error report of a run, the tails driver every tails
+// kernel runs (tail_units), and the checks of a list against the unit
+// directory.  The item drivers are in p4_lists_items.h.  Device code only:
+// included by *.hip files (internal).
 #pragma once
 
 #include "p4_lists.h"
@@ -91,6 +93,40 @@ __device__ __forceinline__ WaveRun wave_run(const uint8_t * in, uint64_t in_byte
     return R;
 }
 
+// The list (selection, query) of every unit of a wave's run of units, from the
+// unit records: lane t holds rec_word, the record of unit first + t (0 past
+// the run).  A head inside the run names its list, the units after it follow
+// by a max-scan, and the units before the run's first head belong to the list
+// of unit `first`: its own head, or one search over base_table[0 .. n].
+__device__ __forceinline__ uint32_t run_ids(uint32_t rec_word, const uint32_t * __restrict base_table, uint64_t n, uint64_t first, uint32_t t)
+{
+    const uint32_t r0 = rl(rec_word, 0) & kRecList;
+    const uint32_t j0 = r0 != 0u ? r0 - 1u : find_list(base_table, static_cast<uint32_t>(n), static_cast<uint32_t>(first), t);
+    return umax32(wave_incl_max(rec_word & kRecList), j0 + 1u) - 1u;
+}
+
+// Where a run's full blocks go.  The output of a lists decode is dense, so the
+// values of a run are one contiguous range: one buffer descriptor from the
+// run's first value to the end of its last full block, 16 bytes per lane at a
+// position that is only 4-byte aligned, stores past the range dropped.  Lane
+// t's unit starts at value `opos` of `out`.
+struct RunOut
+{
+    __amdgpu_buffer_rsrc_t rs;
+    uint32_t rel; // lane t's unit: bytes from the run's first value
+
+    __device__ __forceinline__ RunOut() : rs(make_rsrc(nullptr, 0u)), rel(0u) {} // nothing is stored
+    __device__ __forceinline__ RunOut(uint32_t * out, uint64_t opos, uint64_t fullmask)
+    {
+        const uint64_t opos0 = readlane_u64(opos, 0);
+        rel = static_cast<uint32_t>(opos - opos0) * 4u;
+        const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
+        rs = make_rsrc(out + opos0, rl(rel, lastf) + 1024u);
+    }
+    // unit jj's block, lane t holding values 4t .. 4t + 3
+    __device__ __forceinline__ void store(uint32_t jj, uint32_t t, const u32x4 & x) const { st16_run(rs, rl(rel, jj) + 16u * t, x); }
+};
+
 // Unit jj of a run out of the pipeline: staged into the wave's slot, decoded
 // into registers, delta-1 applied from `start`, and its parsed length held
 // against its offsets (a mismatch sets bit jj of badmask).  The caller stores
@@ -140,6 +176,65 @@ __device__ __forceinline__ void report_bad_units(unsigned long long * err, uint6
         if (t == 0)
             atomicMin(err, static_cast<unsigned long long>(m));
     }
+}
+
+// The tails driver: a wave's run of up to kRunDefault tail units through the
+// generic decoder's pipeline (k_dec_gr, p4_generic.hip).  Lane t of run R
+// holds item first + t's tail -- source unit su of cnt values (`has`; hasmask
+// its ballot, not 0) -- or nothing.  The offsets of the lanes' units are
+// loaded and the run plane is set up, then start() does what else the kernel
+// gathers per lane -- behind the offsets' loads -- and gives the lane's
+// delta-1 start (any value in the plain form), the first chunks go in flight,
+// and every unit of hasmask is decoded into registers and handed to sink(jj,
+// cj, vals): unit jj of the run, its count, lane t holding values t + 64q.
+// The wave_lds_sync() before the next unit is staged is the driver's; a sink
+// that goes through LDS itself keeps its own inner sync.  A lane outside
+// hasmask loads nothing.  Parse errors are reported by source unit.  (The
+// values stay a local of the consume lambda: see TailVals.)
+template <bool D1, uint32_t NC, class Start, class Sink>
+__device__ __forceinline__ void tail_units(const WaveRun & R, const uint64_t * __restrict off, bool has, uint64_t hasmask, uint32_t su,
+                                           uint32_t cnt, uint32_t * slot, uint32_t * scr, unsigned long long * err, Start && start,
+                                           Sink && sink)
+{
+    const uint32_t t = R.t;
+    const uint64_t o = has ? off[su] : 0ull;
+    const uint64_t e = has ? off[su + 1u] : 0ull;
+    RunPlaneT<kListSlot> P;
+    P.init(R.in_base, R.in_end, o, e, has);
+    const uint32_t startv = start();
+    uint64_t badmask = 0u;
+    Chunk C[NC];
+    pipe_prime<NC>(P, C, t);
+    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
+        if (((hasmask >> jj) & 1ull) == 0ull)
+            return;
+        const uint32_t cj = rl(cnt, jj);
+        TailVals x;
+        decode_tail_unit<D1>(P, c, jj, slot, scr, cj, rl(startv, jj), t, x, badmask);
+        sink(jj, cj, x);
+        wave_lds_sync();
+    });
+    report_bad_units(err, badmask, su, t);
+}
+
+// The sink of a tails kernel that stores the values: unit jj's cj values at
+// base + lane jj's opos (read when a unit is stored: start() may set it).  NT:
+// non-temporal, for an output that is not read again by the call.
+template <bool NT>
+__device__ __forceinline__ auto tail_store(uint32_t * base, const uint64_t & opos, uint32_t t)
+{
+    return [base, &opos, t](uint32_t jj, uint32_t cj, const TailVals & x) {
+        uint32_t * op = base + readlane_u64(opos, jj);
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+            if (t + 64u * q < cj)
+            {
+                if constexpr (NT)
+                    __builtin_nontemporal_store(x.v[q], op + t + 64u * q);
+                else
+                    op[t + 64u * q] = x.v[q];
+            }
+    };
 }
 
 // List j against the unit directory: j names a list, its pointers and its

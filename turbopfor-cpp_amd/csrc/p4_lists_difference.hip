@@ -171,18 +171,16 @@ struct DfWs
 // nq sizes no array: the queries are read where they lie
 size_t lists_difference_workspace(uint64_t /*nq*/, uint64_t probe_values) { return DfWs(nullptr, probe_values).bytes; }
 
-hipError_t launch_lists_difference(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                   const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                                   const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
-                                   uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx, uint32_t * out_tpos,
-                                   void * ws, unsigned long long * err, hipStream_t s)
+hipError_t launch_lists_difference(const ListsIndex & X, const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr,
+                                   const uint32_t * qlist, uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr,
+                                   uint32_t * out_pidx, uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s)
 {
     if (nq == 0)
     {
         hipError_t e = err ? fill_u32(err, 0xFFFFFFFFu, 2, s) : hipSuccess;
         return e != hipSuccess ? e : (out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess);
     }
-    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull)
+    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || X.nlists > 0x7FFFFFFFull || X.nunits > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const DfWs W(ws, pv);
     const uint64_t nruns = (pv + 63u) / 64u;
@@ -192,24 +190,23 @@ hipError_t launch_lists_difference(const uint8_t * in, uint64_t in_bytes, const 
     if (e != hipSuccess)
         return e;
     // ---- the lookup: the intersection's plan, items and decode, every probe value's q recorded
-    if ((e = launch_ix_plan(ptr, list_unit, nlists, nunits, unit_last, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
+    if ((e = launch_ix_plan(X, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
         return e;
     if ((e = launch_items(pv, W.hdr, W.pu, W.pl, W.scani, W.ihead, W.iend, W.res, s)) != hipSuccess)
         return e;
-    const dev::IxArgs A{in, in_bytes, off, nunits, ptr, list_unit, start0, unit_last, probe, pv, W.hdr, W.pu, W.pl, W.ihead, W.iend,
-                        W.res, err};
+    const dev::IxArgs A{.it = {.ix = X, .hdr = W.hdr, .pu = W.pu, .pl = W.pl, .ihead = W.ihead, .iend = W.iend, .err = err},
+                        .probe = probe,
+                        .pv = pv,
+                        .res = W.res};
     if ((e = launch_ix_lookup(A, true, s)) != hipSuccess)
         return e;
     // ---- the misses: flags, their run scan (hdr->spare = d_out_ptr[nq]), the compaction
-    hipLaunchKernelGGL(dev::k_df_flags, dim3(rgrid), dim3(256), 0, s, pv, probe_ptr, nq, W.hdr, W.pu, W.res, W.scanm.tot);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_df_flags, rgrid, 256, s, pv, probe_ptr, nq, W.hdr, W.pu, W.res, W.scanm.tot)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u32_single(W.scanm.tot, nruns, W.scanm.pre, W.scanm.tile, &W.hdr->spare, s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_df_out, dim3(flat_grid(std::max(nq + 1u, pv), s)), dim3(256), 0, s, ptr, list_unit, nunits, probe, pv,
-                       probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, W.res, W.scanm.pre, W.scanm.tile, out, out_values, out_ptr, out_pidx,
-                       out_tpos, err);
-    return hipGetLastError();
+    return launch(dev::k_df_out, flat_grid(std::max(nq + 1u, pv), s), 256, s, X.ptr, X.list_unit, X.nunits, probe, pv, probe_ptr, qlist, nq,
+                  W.hdr, W.pu, W.pl, W.res, W.scanm.pre, W.scanm.tile, out, out_values, out_ptr, out_pidx, out_tpos, err);
 }
 
 } // namespace tpf

@@ -97,6 +97,7 @@ struct UnitRun
     __device__ __forceinline__ void lists(const ListsEncArgs & A, uint64_t first, uint32_t t)
     {
         const uint32_t u = static_cast<uint32_t>(first) + t;
+        // (run_ids, p4_lists_dev.h, stated in place: the encoder's kernels were left as they are)
         const uint32_t r0 = rl32(r_, 0) & kRecList;
         const uint32_t j0 = r0 != 0u ? r0 - 1u : find_list(A.ubase, static_cast<uint32_t>(A.nlists), static_cast<uint32_t>(first), t);
         const uint32_t id = umax32(wave_incl_max(r_ & kRecList), j0 + 1u) - 1u;
@@ -459,41 +460,51 @@ struct ListsEncWs
 
 size_t lists_enc_workspace(uint64_t nunits, uint64_t nlists) { return ListsEncWs(nullptr, nunits, nlists).bytes; }
 
+namespace
+{
 // the passes after the structure: tails plan, full plan, run scan, full write, tails write
-static hipError_t lists_enc_passes(const dev::ListsEncArgs & A, const ListsEncWs & W, bool d1, hipStream_t s)
+hipError_t lists_enc_passes(const dev::ListsEncArgs & A, const ListsEncWs & W, bool d1, hipStream_t s)
 {
     hipError_t e;
-    const uint64_t nunits = A.nunits, nlists = A.nlists;
-    const uint32_t grid = static_cast<uint32_t>((nunits + 4u * dev::kLencRun - 1u) / (4u * dev::kLencRun));
-    const uint32_t tgrid = static_cast<uint32_t>((nlists + 4u * dev::kLencTailRun - 1u) / (4u * dev::kLencTailRun));
-    if (d1)
-        hipLaunchKernelGGL((dev::k_lenc_tails<true, false>), dim3(tgrid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL((dev::k_lenc_tails<false, false>), dim3(tgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    const uint64_t nunits = A.nunits;
+    const uint32_t grid = wave_grid(nunits, dev::kLencRun), tgrid = wave_grid(A.nlists, dev::kLencTailRun);
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_lenc_tails<D1, false>; }, tgrid, 256, s, A)) != hipSuccess)
         return e;
-    if (d1)
-        hipLaunchKernelGGL(dev::k_lenc_plan<true>, dim3(grid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL(dev::k_lenc_plan<false>, dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_lenc_plan<D1>; }, grid, 256, s, A)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u64(W.uscan.tot, lenc_runs(nunits), W.uscan.pre, W.uscan.tile,
                                  reinterpret_cast<uint64_t *>(&W.hdr->bytes), s))
         != hipSuccess)
         return e;
-    if (d1)
-        hipLaunchKernelGGL(dev::k_lenc_write<true>, dim3(grid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL(dev::k_lenc_write<false>, dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_lenc_write<D1>; }, grid, 256, s, A)) != hipSuccess)
         return e;
-    if (d1)
-        hipLaunchKernelGGL((dev::k_lenc_tails<true, true>), dim3(tgrid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL((dev::k_lenc_tails<false, true>), dim3(tgrid), dim3(256), 0, s, A);
-    return hipGetLastError();
+    return launch_by(d1, [](auto D1) { return dev::k_lenc_tails<D1, true>; }, tgrid, 256, s, A);
 }
+
+// the arguments over workspace W: `nunits` the unit count, or with devn its capacity
+dev::ListsEncArgs lists_enc_args(const ListsEncWs & W, const uint32_t * in, const uint64_t * ptr, uint64_t nlists, const uint32_t * start0,
+                                 uint64_t nunits, uint8_t * out, uint64_t out_cap, uint64_t * off, unsigned long long * err, uint32_t devn)
+{
+    return dev::ListsEncArgs{.in = in,
+                             .ptr = ptr,
+                             .nlists = nlists,
+                             .start0 = start0,
+                             .nunits = nunits,
+                             .hdr = W.hdr,
+                             .rec = W.rec,
+                             .ubase = W.ubase,
+                             .sz = W.sz,
+                             .plan = W.plan,
+                             .run_tot = W.uscan.tot,
+                             .run_pre = W.uscan.pre,
+                             .run_tile = W.uscan.tile,
+                             .out = out,
+                             .out_cap = out_cap,
+                             .off = off,
+                             .err = err,
+                             .devn = devn};
+}
+} // namespace
 
 // 11 launches whatever the lists: header reset, plan, 2 x run scan, heads
 // (launch_lists_structure), tails plan, full plan, 2 x run scan, full write,
@@ -511,13 +522,8 @@ hipError_t launch_lists_enc(const uint32_t * in, uint64_t in_values, const uint6
     if (e != hipSuccess)
         return e;
     if (nunits == 0)
-    {
-        hipLaunchKernelGGL(dev::k_lenc_empty, dim3(1), dim3(64), 0, s, W.hdr, off);
-        return hipGetLastError();
-    }
-    const dev::ListsEncArgs A{in, ptr, nlists, start0, nunits, W.hdr, W.rec, W.ubase, W.sz, W.plan, W.uscan.tot, W.uscan.pre,
-                              W.uscan.tile, out, out_cap, off, err, 0u};
-    return lists_enc_passes(A, W, d1, s);
+        return launch(dev::k_lenc_empty, 1, 64, s, W.hdr, off);
+    return lists_enc_passes(lists_enc_args(W, in, ptr, nlists, start0, nunits, out, out_cap, off, err, 0u), W, d1, s);
 }
 
 // The encode of lists whose structure a caller planned on the device (the
@@ -534,9 +540,7 @@ hipError_t launch_lists_enc_planned(const uint32_t * in, const uint64_t * ptr, u
                                     uint8_t * out, uint64_t out_cap, uint64_t * off, uint64_t units_cap, void * ws, hipStream_t s)
 {
     const ListsEncWs W(ws, units_cap, nlists);
-    const dev::ListsEncArgs A{in, ptr, nlists, start0, units_cap, W.hdr, W.rec, W.ubase, W.sz, W.plan, W.uscan.tot, W.uscan.pre,
-                              W.uscan.tile, out, out_cap, off, nullptr, 1u};
-    return lists_enc_passes(A, W, d1, s);
+    return lists_enc_passes(lists_enc_args(W, in, ptr, nlists, start0, units_cap, out, out_cap, off, nullptr, 1u), W, d1, s);
 }
 
 } // namespace tpf

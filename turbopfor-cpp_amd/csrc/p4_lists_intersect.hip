@@ -4,17 +4,15 @@
 // values that are also in the target, with their positions.  Every probe value
 // is looked up in the skip table (the first unit of its list whose last value
 // is >= it); consecutive probe values that land in the same unit form an ITEM
-// (p4_lists_items.hip), and every item's unit is decoded once -- with
-// k_un_dec's and k_un_tails's pipelines (p4_lists_units.hip), the start taken
-// from the table -- into the wave's LDS, where the item's probe values are
-// searched 64 at a time.  No decoded block goes to global memory.  Nothing
-// here is sized by the index: grids and the workspace follow nq and
-// probe_values.
+// (p4_lists_items.hip), and every item's unit is decoded once -- by the item
+// drivers (p4_lists_items.h), the start taken from the table -- into the
+// wave's LDS, where the item's probe values are searched 64 at a time.  No
+// decoded block goes to global memory.  Nothing here is sized by the index:
+// grids and the workspace follow nq and probe_values.
 #include "p4_lists.h"
 
-#include "p4_dec256v32.h"
-#include "p4_lists_dev.h"
 #include "p4_lists_host.h"
+#include "p4_lists_items.h"
 
 namespace tpf::dev
 {
@@ -23,10 +21,10 @@ constexpr uint32_t kIxMiss = kItemNone; // result word before the hits pass: not
 constexpr uint32_t kIxHit = 0x100u;     // result word after the hits pass: bits 0-7 p, bit 8 hit, bits 16-22 hits before it in its run
 // (EVERY, the union's lookup: every probe value of an item gets q | kIxFound, p4_lists.h)
 
-// Full blocks: items per wave and chunks in flight.  A wave waits for its
-// item's probe values once per block (that load sits behind the chunk loads in
-// issue order), so short runs over many waves hide the wait better than
-// k_un_dec's 16 blocks per wave; DESIGN.md 4.11 has both timings.
+// Full blocks (item_full_units): items per wave and chunks in flight.  A wave
+// waits for its item's probe values once per block, so short runs over many
+// waves hide the wait better than k_un_dec's 16 blocks per wave; DESIGN.md
+// 4.11 has both timings.
 constexpr uint32_t kIxRun = 4;
 constexpr uint32_t kIxNC = 4;
 
@@ -111,135 +109,29 @@ __device__ __forceinline__ void ix_test(const uint32_t * vals, uint32_t cnt, con
     }
 }
 
-// Full blocks: every wave takes runs of RUN consecutive ITEMS through the
-// k_dec256v32w pipeline, as k_un_dec does with virtual units.  Lane t
-// gathers item first + t: its head's unit word and list, the offsets of the
-// source unit and its start (unit_start, p4_lists_dev.h).  The plan checked
-// list < nlists and list_unit[list] <= su < list_unit[list + 1] <= nunits for
-// every value it gave a unit.  Where k_un_dec stores the block, this keeps it
-// in 1 KB of LDS per wave.
+// Full blocks and tails: the item drivers (p4_lists_items.h) with ix_test as
+// what is done with an item's decoded unit.  A tail's words past its count
+// hold 0xFFFFFFFF, so the lower bound of every value lies inside the count.
 template <uint32_t RUN, uint32_t NC, int MINW, bool EVERY>
 __global__ __launch_bounds__(256, MINW) void k_ix_dec(const IxArgs A)
 {
-    __shared__ uint32_t slots[4][kSlotBytes / 4];
-    __shared__ uint32_t scratch[4][kWaveScratchU32];
-    __shared__ uint32_t vals[4][256];
-    // per item of the run, read back wave-uniformly: the source unit (for the
-    // error report only, as in k_un_dec), the probe range and the start -- held
-    // in registers across the pipeline they cost spilled VGPRs at 7 waves
-    __shared__ uint32_t srcu[4][RUN], itemh[4][RUN], iteme[4][RUN], starts[4][RUN];
-    if (!items_go(A.hdr))
+    if (!items_go(A.it.hdr))
         return;
     constexpr uint32_t kRun = RUN;
-    const uint64_t nit = A.hdr->nitems;
-    WaveRun R = wave_run(A.in, A.in_bytes, kRun, nit);
-    const uint32_t t = R.t, wv = R.wv;
-    uint32_t * slot = slots[wv];
-    uint32_t * scr = scratch[wv];
-    // the host knows only the cap of one item per probe value: the grid covers
-    // the device and every wave strides over the runs of the real item count
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * 4u * kRun;
-    for (; R.first < nit; R.seek(R.first + stride, kRun, nit))
-    {
-        const uint64_t first = R.first;
-        const bool valid = t < R.n;
-        const uint32_t ih = valid ? A.ihead[first + t] : 0u;
-        const uint32_t ie = valid ? A.iend[first + t] : 0u;
-        const uint32_t w = valid ? A.pu[ih] : kItemNone;
-        const bool full = valid && (w & kRecTail) == 0u;
-        const uint64_t fullmask = __ballot(full);
-        if (fullmask == 0ull)
-            continue; // a run of tails only
-        const uint32_t su = w & kRecList;
-        const uint32_t lj = full ? A.pl[ih] : 0u;
-        const uint64_t o = full ? A.off[su] : 0ull;
-        const uint64_t e = full ? A.off[su + 1u] : 0ull;
-        RunPlaneT<kSlotBytes, true> P;
-        P.init(R.in_base, R.in_end, o, e, full);
-        {
-            uint32_t startv = 0u;
-            if (full)
-                startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
-            if (t < kRun)
-            {
-                srcu[wv][t] = full ? su : 0xFFFFFFFFu;
-                itemh[wv][t] = ih;
-                iteme[wv][t] = ie;
-                starts[wv][t] = startv;
-            }
-        }
-        wave_lds_sync();
-        Chunk C[NC];
-        pipe_prime<NC>(P, C, t);
-
-        uint64_t badmask = 0u;
-        pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-            if (((fullmask >> jj) & 1ull) == 0ull)
-                return;
-            u32x4 x;
-            decode_full_unit<true>(P, c, jj, slot, scr, uni(starts[wv][jj]), t, x, badmask);
-            reinterpret_cast<u32x4 *>(vals[wv])[t] = x;
-            wave_lds_sync();
-            ix_test<EVERY>(vals[wv], 256u, A.probe, A.res, uni(itemh[wv][jj]), uni(iteme[wv][jj]), t);
-            wave_lds_sync();
-        });
-        report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
-        wave_lds_sync(); // the item words are rewritten by the next run
-    }
+    item_full_units<true, RUN, NC>(A.it, stride, [&](const uint32_t * vals, uint32_t cnt, uint32_t h, uint32_t e, uint32_t t) {
+        ix_test<EVERY>(vals, cnt, A.probe, A.res, h, e, t);
+    });
 }
 
-// Tails: every wave owns kRunDefault consecutive ITEMS with the generic
-// decoder's pipeline, as k_un_tails does for selections; lane t holds item
-// first + t when its unit is its list's p4Enc32 tail, n % 256 values.
 template <uint32_t NC, bool EVERY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ix_tails(const IxArgs A)
 {
-    __shared__ uint32_t slots[4][kListSlot / 4];
-    __shared__ uint32_t scratch[4][kListScratchU32];
-    __shared__ uint32_t vals[4][256];
-    if (!items_go(A.hdr))
+    if (!items_go(A.it.hdr))
         return;
-    const uint64_t nit = A.hdr->nitems;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, nit);
-    const uint32_t t = R.t, wv = R.wv;
-    if (R.first >= nit)
-        return;
-    uint32_t * slot = slots[wv];
-    const bool valid = t < R.n;
-    const uint32_t ih = valid ? A.ihead[R.first + t] : 0u;
-    const uint32_t ie = valid ? A.iend[R.first + t] : 0u;
-    const uint32_t w = valid ? A.pu[ih] : 0u;
-    const bool has = valid && (w & kRecTail) != 0u;
-    const uint64_t hasmask = __ballot(has);
-    if (hasmask == 0ull)
-        return;
-    const uint32_t su = w & kRecList;
-    const uint32_t lj = has ? A.pl[ih] : 0u;
-    const uint32_t cnt = has ? static_cast<uint32_t>((A.ptr[lj + 1u] - A.ptr[lj]) & 255u) : 0u; // != 0: the plan saw a tail
-    const uint64_t o = has ? A.off[su] : 0ull;
-    const uint64_t e = has ? A.off[su + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
-    uint32_t startv = 0u;
-    if (has)
-        startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals x;
-        decode_tail_unit<true>(P, c, jj, slot, scratch[wv], cj, rl(startv, jj), t, x, badmask);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            vals[wv][t + 64u * q] = t + 64u * q < cj ? x.v[q] : 0xFFFFFFFFu;
-        wave_lds_sync();
-        ix_test<EVERY>(vals[wv], cj, A.probe, A.res, rl(ih, jj), rl(ie, jj), t);
-        wave_lds_sync();
+    item_tail_units<true, NC>(A.it, 0xFFFFFFFFu, [&](const uint32_t * vals, uint32_t cnt, uint32_t h, uint32_t e, uint32_t t) {
+        ix_test<EVERY>(vals, cnt, A.probe, A.res, h, e, t);
     });
-    report_bad_units(A.err, badmask, su, t);
 }
 
 // Hits: every wave owns 64 consecutive probe indices again; the hit flags'
@@ -352,53 +244,39 @@ struct IxWs
 // nq sizes no array: the queries are read where they lie
 size_t lists_intersect_workspace(uint64_t /*nq*/, uint64_t probe_values) { return IxWs(nullptr, probe_values).bytes; }
 
-hipError_t launch_ix_plan(const uint64_t * ptr, const uint32_t * list_unit, uint64_t nlists, uint64_t nunits, const uint32_t * unit_last,
-                          const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
-                          dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s)
+hipError_t launch_ix_plan(const ListsIndex & X, const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist,
+                          uint64_t nq, dev::ItemHdr * hdr, uint32_t * pu, uint32_t * pl, hipStream_t s)
 {
-    hipLaunchKernelGGL(dev::k_ix_plan, dim3(flat_grid(std::max(nq, pv), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, unit_last,
-                       probe, pv, probe_ptr, qlist, nq, hdr, pu, pl);
-    return hipGetLastError();
+    return launch(dev::k_ix_plan, flat_grid(std::max(nq, pv), s), 256, s, X.ptr, X.list_unit, X.nlists, X.nunits, X.unit_last, probe, pv,
+                  probe_ptr, qlist, nq, hdr, pu, pl);
 }
-
-namespace
-{
-template <bool EVERY>
-hipError_t ix_lookup(const dev::IxArgs & A, uint32_t dgrid, uint32_t igrid, hipStream_t s)
-{
-    hipLaunchKernelGGL((dev::k_ix_dec<dev::kIxRun, dev::kIxNC, dev::kListsMinW, EVERY>), dim3(dgrid), dim3(256), 0, s, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_ix_tails<dev::kTailsNC, EVERY>), dim3(igrid), dim3(256), 0, s, A);
-    return hipGetLastError();
-}
-} // namespace
 
 hipError_t launch_ix_lookup(const dev::IxArgs & A, bool every, hipStream_t s)
 {
     const uint64_t pv = A.pv;
     // one wave per kRunDefault items: at least one workgroup for an empty probe
-    const uint32_t igrid = static_cast<uint32_t>(std::max<uint64_t>(1, (pv + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault)));
+    const uint32_t igrid = std::max(1u, wave_grid(pv, dev::kRunDefault));
     // the cap is one item per probe value, a dense probe holds hundreds of times fewer: at most kListsMinW
     // workgroups per CU, whose waves stride over the real items (k_ix_tails: a wave per 16 items of the cap)
     const uint32_t dgrid = static_cast<uint32_t>(std::max<uint64_t>(
         1, std::min<uint64_t>((pv + 4u * dev::kIxRun - 1u) / (4u * dev::kIxRun), grid_cap(s, dev::kListsMinW))));
-    return every ? ix_lookup<true>(A, dgrid, igrid, s) : ix_lookup<false>(A, dgrid, igrid, s);
+    const hipError_t e
+        = launch_by(every, [](auto EVERY) { return dev::k_ix_dec<dev::kIxRun, dev::kIxNC, dev::kListsMinW, EVERY>; }, dgrid, 256, s, A);
+    if (e != hipSuccess)
+        return e;
+    return launch_by(every, [](auto EVERY) { return dev::k_ix_tails<dev::kTailsNC, EVERY>; }, igrid, 256, s, A);
 }
 
-hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                  const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                                  const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
-                                  uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx, uint32_t * out_tpos,
-                                  void * ws, unsigned long long * err, hipStream_t s)
+hipError_t launch_lists_intersect(const ListsIndex & X, const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr,
+                                  const uint32_t * qlist, uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr,
+                                  uint32_t * out_pidx, uint32_t * out_tpos, void * ws, unsigned long long * err, hipStream_t s)
 {
     if (nq == 0)
     {
         hipError_t e = err ? fill_u32(err, 0xFFFFFFFFu, 2, s) : hipSuccess;
         return e != hipSuccess ? e : (out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess);
     }
-    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull)
+    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || X.nlists > 0x7FFFFFFFull || X.nunits > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const IxWs W(ws, pv);
     const uint64_t nruns = (pv + 63u) / 64u;
@@ -407,22 +285,22 @@ hipError_t launch_lists_intersect(const uint8_t * in, uint64_t in_bytes, const u
     hipError_t e = launch_items_reset(err, W.hdr, s);
     if (e != hipSuccess)
         return e;
-    if ((e = launch_ix_plan(ptr, list_unit, nlists, nunits, unit_last, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
+    if ((e = launch_ix_plan(X, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
         return e;
     if ((e = launch_items(pv, W.hdr, W.pu, W.pl, W.scani, W.ihead, W.iend, W.res, s)) != hipSuccess)
         return e;
-    const dev::IxArgs A{in, in_bytes, off, nunits, ptr, list_unit, start0, unit_last, probe, pv, W.hdr, W.pu, W.pl, W.ihead, W.iend,
-                        W.res, err};
+    const dev::IxArgs A{.it = {.ix = X, .hdr = W.hdr, .pu = W.pu, .pl = W.pl, .ihead = W.ihead, .iend = W.iend, .err = err},
+                        .probe = probe,
+                        .pv = pv,
+                        .res = W.res};
     if ((e = launch_ix_lookup(A, false, s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_ix_hits, dim3(rgrid), dim3(256), 0, s, pv, W.hdr, W.res, W.scanh.tot);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_ix_hits, rgrid, 256, s, pv, W.hdr, W.res, W.scanh.tot)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u32_single(W.scanh.tot, nruns, W.scanh.pre, W.scanh.tile, &W.hdr->spare, s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_ix_out, dim3(flat_grid(std::max(nq + 1u, pv), s)), dim3(256), 0, s, list_unit, nunits, probe, pv, probe_ptr,
-                       nq, W.hdr, W.pu, W.pl, W.res, W.scanh.pre, W.scanh.tile, out, out_values, out_ptr, out_pidx, out_tpos, err);
-    return hipGetLastError();
+    return launch(dev::k_ix_out, flat_grid(std::max(nq + 1u, pv), s), 256, s, X.list_unit, X.nunits, probe, pv, probe_ptr, nq, W.hdr, W.pu,
+                  W.pl, W.res, W.scanh.pre, W.scanh.tile, out, out_values, out_ptr, out_pidx, out_tpos, err);
 }
 
 } // namespace tpf

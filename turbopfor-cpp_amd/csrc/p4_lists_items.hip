@@ -2,11 +2,11 @@
 // and the gather (p4_lists_gather.hip) share (p4_lists.h): the
 // entry's plan leaves, per request index, the source unit and the list it
 // names; consecutive indices that name the same unit of the same list form an
-// ITEM, whose unit the entry's decode kernels then decode once.
+// ITEM, whose unit the entry's decode kernels then decode once (the item
+// drivers, p4_lists_items.h).
 #include "p4_lists.h"
 
-#include "p4_scan.h"
-#include "tpf_kernels.h"
+#include "p4_lists_host.h"
 
 namespace tpf::dev
 {
@@ -84,8 +84,7 @@ namespace tpf
 
 hipError_t launch_items_reset(unsigned long long * err, dev::ItemHdr * hdr, hipStream_t s)
 {
-    hipLaunchKernelGGL(dev::k_items_reset, dim3(1), dim3(64), 0, s, err, hdr);
-    return hipGetLastError();
+    return launch(dev::k_items_reset, 1, 64, s, err, hdr);
 }
 
 hipError_t launch_items(uint64_t pv, dev::ItemHdr * hdr, const uint32_t * pu, const uint32_t * pl, const RunScanWs<uint32_t> & scan,
@@ -94,17 +93,12 @@ hipError_t launch_items(uint64_t pv, dev::ItemHdr * hdr, const uint32_t * pu, co
     const uint64_t nruns = (pv + 63u) / 64u;
     // one wave per 64 request indices: at least one workgroup for an empty request
     const uint32_t rgrid = static_cast<uint32_t>(std::max<uint64_t>(1, (nruns + 3u) / 4u));
-    if (res != nullptr)
-        hipLaunchKernelGGL(dev::k_item_heads<true>, dim3(rgrid), dim3(256), 0, s, pv, hdr, pu, pl, scan.tot, res);
-    else
-        hipLaunchKernelGGL(dev::k_item_heads<false>, dim3(rgrid), dim3(256), 0, s, pv, hdr, pu, pl, scan.tot, res);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_by(res != nullptr, [](auto RES) { return dev::k_item_heads<RES>; }, rgrid, 256, s, pv, hdr, pu, pl, scan.tot, res);
     if (e != hipSuccess)
         return e;
     if ((e = launch_run_scan_u32_single(scan.tot, nruns, scan.pre, scan.tile, &hdr->nitems, s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_item_items, dim3(rgrid), dim3(256), 0, s, pv, hdr, pu, pl, scan.pre, scan.tile, ihead, iend);
-    return hipGetLastError();
+    return launch(dev::k_item_items, rgrid, 256, s, pv, hdr, pu, pl, scan.pre, scan.tile, ihead, iend);
 }
 
 } // namespace tpf

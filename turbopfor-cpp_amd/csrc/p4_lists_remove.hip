@@ -55,15 +55,7 @@ struct RemHdr
 
 struct RemArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * lptr;
-    const uint32_t * lunit;
-    uint64_t n; // nlists
-    const uint32_t * start0;
-    const uint32_t * unit_last;
+    ListsIndex ix; // (the result has ix.nlists lists too)
     const uint32_t * pos;
     uint64_t pos_values;
     const uint64_t * pptr;
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(256) void k_rem_reset(const RemArgs A)
         *A.hdr = RemHdr{~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0u, 0u};
         *A.ehdr = ListsHdr{0ull, 0ull}; // no go until the heads pass says so
     }
-    for (uint64_t j = gid; j < A.n; j += gsz)
+    for (uint64_t j = gid; j < A.ix.nlists; j += gsz)
         A.qof[j] = kItemNone;
 }
 
@@ -159,14 +151,14 @@ __global__ __launch_bounds__(256) void k_rem_plan_q(const RemArgs A)
     {
         const uint32_t j = A.qlist[k];
         const uint64_t pa = A.pptr[k], pb = A.pptr[k + 1u];
-        bool bad = j >= A.n || (k != 0u && j <= A.qlist[k - 1u]) || pb < pa || pb > A.pos_values;
+        bool bad = j >= A.ix.nlists || (k != 0u && j <= A.qlist[k - 1u]) || pb < pa || pb > A.pos_values;
         uint32_t sj = 0u, uf = 0u, uc = 0u;
         if (!bad)
         {
             uint64_t n;
             uint32_t ua, ub;
             // a list that fails here fails the list plan, whose code is the lower one
-            const bool dir = list_dir_ok(A.lptr, A.lunit, A.n, A.nunits, j, &n, &ua, &ub);
+            const bool dir = list_dir_ok(A.ix.ptr, A.ix.list_unit, A.ix.nlists, A.ix.nunits, j, &n, &ua, &ub);
             if (dir && pb != pa)
             {
                 const uint64_t p0 = A.pos[pa];
@@ -215,9 +207,9 @@ __global__ __launch_bounds__(256) void k_rem_plan_p(const RemArgs A)
     if (k == kItemNone)
         return; // pointers that descend: the query plan refuses them
     const uint32_t j = A.qlist[k];
-    if (j >= A.n)
+    if (j >= A.ix.nlists)
         return;
-    const uint64_t n = A.lptr[j + 1u] - A.lptr[j];
+    const uint64_t n = A.ix.ptr[j + 1u] - A.ix.ptr[j];
     const uint32_t v = A.pos[p];
     if (v >= n || (p > A.pptr[k] && A.pos[p - 1u] >= v))
         atomicMin(&A.hdr->qbad, static_cast<unsigned long long>(k));
@@ -230,13 +222,13 @@ __global__ __launch_bounds__(256) void k_rem_plan_l(const RemArgs A)
     const uint32_t t = threadIdx.x & 63u;
     uint32_t keep = 0u, nu = 0u, tq = 0u;
     uint64_t kb = 0ull;
-    if (j < A.n)
+    if (j < A.ix.nlists)
     {
-        const uint64_t p0 = A.lptr[j], p1 = A.lptr[j + 1u];
+        const uint64_t p0 = A.ix.ptr[j], p1 = A.ix.ptr[j + 1u];
         const uint64_t oldn = p1 - p0;
         const uint64_t cnt = (oldn >> 8) + ((oldn & 255u) != 0u ? 1u : 0u);
-        const uint64_t lu0 = A.lunit[j], lu1 = A.lunit[j + 1u];
-        bool bad = p1 < p0 || lu1 - lu0 != cnt || lu1 > A.nunits;
+        const uint64_t lu0 = A.ix.list_unit[j], lu1 = A.ix.list_unit[j + 1u];
+        bool bad = p1 < p0 || lu1 - lu0 != cnt || lu1 > A.ix.nunits;
         if (!bad)
         {
             keep = static_cast<uint32_t>(cnt);
@@ -254,8 +246,8 @@ __global__ __launch_bounds__(256) void k_rem_plan_l(const RemArgs A)
             if (cnt != 0u)
             {
                 // the ends of the copied range
-                const uint64_t o0 = A.off[lu0], o1 = A.off[lu0 + keep];
-                bad = o0 > o1 || o1 > A.in_bytes;
+                const uint64_t o0 = A.ix.off[lu0], o1 = A.ix.off[lu0 + keep];
+                bad = o0 > o1 || o1 > A.ix.in_bytes;
                 kb = bad ? 0ull : o1 - o0;
             }
             nu = keep + m;
@@ -265,7 +257,7 @@ __global__ __launch_bounds__(256) void k_rem_plan_l(const RemArgs A)
         A.keep[j] = keep;
     }
     const uint64_t run = j / 64u;
-    if (run * 64u < A.n)
+    if (run * 64u < A.ix.nlists)
     {
         publish_run_total(A.nu_tot, run, nu, t);
         publish_run_total(A.tq_tot, run, tq, t);
@@ -316,7 +308,7 @@ __global__ __launch_bounds__(256) void k_rem_heads_q(const RemArgs A)
         {
             // the staged values continue the list: from the last kept unit, or from start0
             const uint32_t j = A.sel[k], u0 = A.ufirst[k];
-            A.sst[k] = u0 == 0u ? (A.start0 != nullptr ? A.start0[j] : 0u) : A.unit_last[A.lunit[j] + u0 - 1u];
+            A.sst[k] = u0 == 0u ? (A.ix.start0 != nullptr ? A.ix.start0[j] : 0u) : A.ix.unit_last[A.ix.list_unit[j] + u0 - 1u];
         }
     }
     else
@@ -332,15 +324,15 @@ __global__ __launch_bounds__(256) void k_rem_heads_l(const RemArgs A)
 {
     const uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     const RemHdr h = *A.hdr;
-    const uint64_t ebase = A.nunits;
+    const uint64_t ebase = A.ix.nunits;
     const uint32_t verdict = rem_verdict(A, h);
     if (verdict == kRemRefused)
     {
         if (j == 0)
-            rem_err(A.err, h.bad != ~0ull ? ebase + h.bad : ebase + A.n + h.qbad);
+            rem_err(A.err, h.bad != ~0ull ? ebase + h.bad : ebase + A.ix.nlists + h.qbad);
         return;
     }
-    const bool in = j < A.n;
+    const bool in = j < A.ix.nlists;
     const uint32_t keep = in ? A.keep[j] : 0u;
     const uint32_t k = in ? A.qof[j] : kItemNone;
     const uint32_t tq = k != kItemNone ? 1u : 0u;
@@ -349,11 +341,11 @@ __global__ __launch_bounds__(256) void k_rem_heads_l(const RemArgs A)
     uint64_t kb = 0ull;
     if (in && keep != 0u)
     {
-        const uint32_t lu = A.lunit[j];
-        kb = A.off[lu + keep] - A.off[lu];
+        const uint32_t lu = A.ix.list_unit[j];
+        kb = A.ix.off[lu + keep] - A.ix.off[lu];
     }
     uint64_t NU = wave_incl_scan(nu) - nu, TQ = wave_incl_scan(tq) - tq, KB = wave_incl_scan64(kb) - kb;
-    if (j > A.n)
+    if (j > A.ix.nlists)
         return;
     if (in)
     {
@@ -368,12 +360,12 @@ __global__ __launch_bounds__(256) void k_rem_heads_l(const RemArgs A)
     }
     // TQ queries name lists before j (every query names a list of its own): their positions are gone
     const uint64_t nr = A.nq != 0u ? A.pptr[TQ] - A.pptr[0] : 0ull;
-    A.lptr_out[j] = (A.lptr[j] - A.lptr[0]) - nr;
+    A.lptr_out[j] = (A.ix.ptr[j] - A.ix.ptr[0]) - nr;
     A.lunit_out[j] = static_cast<uint32_t>(NU);
     if (verdict != kRemGo)
     {
-        if (j == A.n)
-            rem_err(A.err, ebase + A.n + A.nq + (verdict == kRemStage ? 0u : 1u));
+        if (j == A.ix.nlists)
+            rem_err(A.err, ebase + A.ix.nlists + A.nq + (verdict == kRemStage ? 0u : 1u));
         return;
     }
     A.kbpre[j] = KB;
@@ -470,19 +462,19 @@ __global__ __launch_bounds__(256) void k_rem_segs(const RemArgs A)
 {
     const uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     // what the units decode found: a unit of the stream (its own codes lie at or past nunits)
-    if (j == 0 && A.hdr->uerr < A.nunits)
+    if (j == 0 && A.hdr->uerr < A.ix.nunits)
         rem_err(A.err, A.hdr->uerr);
     if (A.hdr->go == 0u)
         return;
-    if (j > A.n)
+    if (j > A.ix.nlists)
         return;
     const uint64_t s = A.kbpre[j] + A.noff[A.subase[j]];
     A.lstart[j] = s;
-    if (j == A.n)
+    if (j == A.ix.nlists)
     {
         A.off_out[A.hdr->nunits_out] = s;
         if (s > A.out_cap)
-            rem_err(A.err, A.nunits + A.n + A.nq + 2u);
+            rem_err(A.err, A.ix.nunits + A.ix.nlists + A.nq + 2u);
         else
             A.hdr->fit = 1u;
     }
@@ -500,18 +492,18 @@ __global__ __launch_bounds__(256) void k_rem_offsets(const RemArgs A)
     if (u - t >= nuo)
         return;
     // the last j with lunit_out[j] <= u (lunit_out[0] = 0 <= u < lunit_out[n])
-    const uint32_t j0 = find_list(A.lunit_out, static_cast<uint32_t>(A.n), static_cast<uint32_t>(u - t), t); // u - t < nuo < 2^31
+    const uint32_t j0 = find_list(A.lunit_out, static_cast<uint32_t>(A.ix.nlists), static_cast<uint32_t>(u - t), t); // u - t < nuo < 2^31
     if (u >= nuo)
         return;
-    const uint64_t j = gallop(A.lunit_out, static_cast<uint32_t>(A.n), j0, u);
+    const uint64_t j = gallop(A.lunit_out, static_cast<uint32_t>(A.ix.nlists), j0, u);
     const uint32_t local = static_cast<uint32_t>(u) - A.lunit_out[j];
-    const uint32_t lu = A.lunit[j];
+    const uint32_t lu = A.ix.list_unit[j];
     const uint32_t keep = A.keep[j];
     if (local < keep)
     {
-        A.off_out[u] = A.lstart[j] + (A.off[lu + local] - A.off[lu]);
+        A.off_out[u] = A.lstart[j] + (A.ix.off[lu + local] - A.ix.off[lu]);
         if constexpr (D1)
-            A.ulast_out[u] = A.unit_last[lu + local];
+            A.ulast_out[u] = A.ix.unit_last[lu + local];
     }
     else
     {
@@ -526,7 +518,7 @@ __global__ __launch_bounds__(256) void k_rem_offsets(const RemArgs A)
 }
 
 // ---- stitch -------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rem_stitch(const RemArgs A) { stitch_tile(A); }
+__global__ __launch_bounds__(256) void k_rem_stitch(const RemArgs A) { stitch_tile(A, A.ix.nlists); }
 
 } // namespace tpf::dev
 
@@ -606,52 +598,86 @@ size_t lists_remove_workspace(uint64_t nlists, uint64_t nq, uint64_t stage_value
 // [offsets,] [stitch] -- 12 -- and with nq != 0 plan q, [plan p,] 2 x 2 run
 // scans, 9 of the units decode, heads q, [compact,] 6 of the encoder -- 23:
 // 35 at the most, 36 with d_err's reset by the entry point.
-hipError_t launch_lists_remove(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * lptr,
-                               const uint32_t * lunit, uint64_t n, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                               const uint32_t * pos, uint64_t pos_values, const uint64_t * pptr, const uint32_t * qlist, uint64_t nq,
-                               uint64_t stage_values, uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap,
-                               uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out, void * ws, unsigned long long * err,
-                               hipStream_t s)
+hipError_t launch_lists_remove(const ListsIndex & X, bool d1, const uint32_t * pos, uint64_t pos_values, const uint64_t * pptr,
+                               const uint32_t * qlist, uint64_t nq, uint64_t stage_values, uint8_t * out, uint64_t out_cap,
+                               uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out,
+                               void * ws, unsigned long long * err, hipStream_t s)
 {
     hipError_t e;
+    const uint64_t n = X.nlists;
     if (n == 0)
-    {
-        hipLaunchKernelGGL(dev::k_rem_empty, dim3(1), dim3(64), 0, s, lptr_out, lunit_out, off_out);
-        return hipGetLastError();
-    }
+        return launch(dev::k_rem_empty, 1, 64, s, lptr_out, lunit_out, off_out);
     const RemCaps C(nq, stage_values);
     const RemWs W(ws, n, nq, stage_values, C);
     const ListsEncPlanView V = lists_enc_plan_view(W.enc, C.units, nq);
-    const dev::RemArgs A{in,        in_bytes,   off,       nunits,     lptr,       lunit,      n,          start0,     unit_last,
-                         pos,       pos_values, pptr,      qlist,      nq,         stage_values, out,      out_cap,    off_out,
-                         units_cap, lptr_out,   lunit_out, ulast_out,  err,        W.hdr,      W.sc.tot,   W.sm.tot,   W.snu.tot,
-                         W.stq.tot, W.skb.tot,  W.sc.pre,  W.sc.tile,  W.sm.pre,   W.sm.tile,  W.snu.pre,  W.snu.tile, W.stq.pre,
-                         W.stq.tile, W.skb.pre, W.skb.tile, W.qof,     W.keep,     W.subase,   W.kbpre,    W.lstart,   W.sel,
-                         W.ufirst,  W.ucount,   W.cq,      W.mq,       W.sst,      W.sptr,     W.dptr,     W.raw,      W.stage,
-                         W.noff,    W.sbytes,   V.hdr,     V.ubase,    V.rec,      C.units};
+    const dev::RemArgs A{.ix = X,
+                         .pos = pos,
+                         .pos_values = pos_values,
+                         .pptr = pptr,
+                         .qlist = qlist,
+                         .nq = nq,
+                         .stage_values = stage_values,
+                         .out = out,
+                         .out_cap = out_cap,
+                         .off_out = off_out,
+                         .units_cap = units_cap,
+                         .lptr_out = lptr_out,
+                         .lunit_out = lunit_out,
+                         .ulast_out = ulast_out,
+                         .err = err,
+                         .hdr = W.hdr,
+                         .c_tot = W.sc.tot,
+                         .m_tot = W.sm.tot,
+                         .nu_tot = W.snu.tot,
+                         .tq_tot = W.stq.tot,
+                         .kb_tot = W.skb.tot,
+                         .c_pre = W.sc.pre,
+                         .c_tile = W.sc.tile,
+                         .m_pre = W.sm.pre,
+                         .m_tile = W.sm.tile,
+                         .nu_pre = W.snu.pre,
+                         .nu_tile = W.snu.tile,
+                         .tq_pre = W.stq.pre,
+                         .tq_tile = W.stq.tile,
+                         .kb_pre = W.skb.pre,
+                         .kb_tile = W.skb.tile,
+                         .qof = W.qof,
+                         .keep = W.keep,
+                         .subase = W.subase,
+                         .kbpre = W.kbpre,
+                         .lstart = W.lstart,
+                         .sel = W.sel,
+                         .ufirst = W.ufirst,
+                         .ucount = W.ucount,
+                         .cq = W.cq,
+                         .mq = W.mq,
+                         .sst = W.sst,
+                         .sptr = W.sptr,
+                         .dptr = W.dptr,
+                         .raw = W.raw,
+                         .stage = W.stage,
+                         .noff = W.noff,
+                         .sbytes = W.sbytes,
+                         .ehdr = V.hdr,
+                         .qsub = V.ubase,
+                         .rec = V.rec,
+                         .su_cap = C.units};
     auto grid = [](uint64_t items, uint64_t per) { return dim3(static_cast<uint32_t>((items + per - 1u) / per)); };
     using u64p = uint64_t *;
-    hipLaunchKernelGGL(dev::k_rem_reset, dim3(flat_grid(n, s)), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_rem_reset, flat_grid(n, s), 256, s, A)) != hipSuccess)
         return e;
     if (nq != 0u)
     {
-        hipLaunchKernelGGL(dev::k_rem_plan_q, grid(std::max(nq, C.units), 256), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
+        if ((e = launch(dev::k_rem_plan_q, grid(std::max(nq, C.units), 256), 256, s, A)) != hipSuccess)
             return e;
-        if (pos_values != 0u)
-        {
-            hipLaunchKernelGGL(dev::k_rem_plan_p, grid(pos_values, 256), dim3(256), 0, s, A);
-            if ((e = hipGetLastError()) != hipSuccess)
-                return e;
-        }
+        if (pos_values != 0u && (e = launch(dev::k_rem_plan_p, grid(pos_values, 256), 256, s, A)) != hipSuccess)
+            return e;
         const uint64_t nqr = rem_runs(nq);
         if ((e = launch_run_scan_u64(W.sc.tot, nqr, W.sc.pre, W.sc.tile, u64p(&W.hdr->c), s)) != hipSuccess
             || (e = launch_run_scan_u64(W.sm.tot, nqr, W.sm.pre, W.sm.tile, u64p(&W.hdr->m), s)) != hipSuccess)
             return e;
     }
-    hipLaunchKernelGGL(dev::k_rem_plan_l, grid(n, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_rem_plan_l, grid(n, 256), 256, s, A)) != hipSuccess)
         return e;
     const uint64_t nr = rem_runs(n);
     if ((e = launch_run_scan_u64(W.snu.tot, nr, W.snu.pre, W.snu.tile, u64p(&W.hdr->nu), s)) != hipSuccess
@@ -661,52 +687,30 @@ hipError_t launch_lists_remove(const uint8_t * in, uint64_t in_bytes, const uint
     if (nq != 0u)
     {
         // the suffixes, every block once from the table; a refused plan leaves ranges the decode refuses or empty ones
-        if ((e = launch_lists_units(in, in_bytes, off, nunits, lptr, lunit, n, d1, start0, unit_last, W.sel, W.ufirst, W.ucount, nq, W.raw,
-                                    stage_values, W.dptr, W.units, reinterpret_cast<unsigned long long *>(&W.hdr->uerr), s))
+        if ((e = launch_lists_units(X, d1, W.sel, W.ufirst, W.ucount, nq, W.raw, stage_values, W.dptr, W.units,
+                                    reinterpret_cast<unsigned long long *>(&W.hdr->uerr), s))
             != hipSuccess)
             return e;
-        if (d1)
-            hipLaunchKernelGGL(dev::k_rem_heads_q<true>, grid(nq + 1u, 256), dim3(256), 0, s, A);
-        else
-            hipLaunchKernelGGL(dev::k_rem_heads_q<false>, grid(nq + 1u, 256), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
+        if ((e = launch_by(d1, [](auto D1) { return dev::k_rem_heads_q<D1>; }, grid(nq + 1u, 256), 256, s, A)) != hipSuccess)
             return e;
     }
-    hipLaunchKernelGGL(dev::k_rem_heads_l, grid(n + 1u, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_rem_heads_l, grid(n + 1u, 256), 256, s, A)) != hipSuccess)
         return e;
     if (nq != 0u)
     {
-        if (stage_values != 0u)
-        {
-            hipLaunchKernelGGL(dev::k_rem_compact, grid(stage_values, 256), dim3(256), 0, s, A);
-            if ((e = hipGetLastError()) != hipSuccess)
-                return e;
-        }
+        if (stage_values != 0u && (e = launch(dev::k_rem_compact, grid(stage_values, 256), 256, s, A)) != hipSuccess)
+            return e;
         if ((e = launch_lists_enc_planned(W.stage, W.sptr, nq, d1, d1 ? W.sst : nullptr, W.sbytes, C.bytes, W.noff, C.units, W.enc, s))
             != hipSuccess)
             return e;
     }
-    hipLaunchKernelGGL(dev::k_rem_segs, grid(n + 1u, 256), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_rem_segs, grid(n + 1u, 256), 256, s, A)) != hipSuccess)
         return e;
-    if (units_cap != 0u)
-    {
-        if (d1)
-            hipLaunchKernelGGL(dev::k_rem_offsets<true>, grid(units_cap, 256), dim3(256), 0, s, A);
-        else
-            hipLaunchKernelGGL(dev::k_rem_offsets<false>, grid(units_cap, 256), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
-            return e;
-    }
+    if (units_cap != 0u && (e = launch_by(d1, [](auto D1) { return dev::k_rem_offsets<D1>; }, grid(units_cap, 256), 256, s, A)) != hipSuccess)
+        return e;
     // the stream is never longer than the old bytes plus the staged ones
-    const uint64_t span = std::min(out_cap, in_bytes + C.bytes);
-    if (span != 0u)
-    {
-        hipLaunchKernelGGL(dev::k_rem_stitch, grid(span, 4u * dev::kListsAppendTile), dim3(256), 0, s, A);
-        e = hipGetLastError();
-    }
-    return e;
+    const uint64_t span = std::min(out_cap, X.in_bytes + C.bytes);
+    return span != 0u ? launch(dev::k_rem_stitch, grid(span, 4u * dev::kListsAppendTile), 256, s, A) : hipSuccess;
 }
 
 } // namespace tpf

@@ -18,11 +18,7 @@ namespace tpf::dev
 
 struct SelArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    const uint32_t * list_unit;
-    const uint32_t * start0;
+    ListsIndex ix;             // (no skip table: delta-1 sums the selected blocks)
     const uint32_t * sel;
     uint64_t nsel;
     uint32_t * out;
@@ -198,11 +194,12 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
     // the run's source units, for the error report only: held in a register
     // across the pipeline they cost the delta-1 form 6 spilled VGPRs at 7 waves
     __shared__ uint32_t srcu[4][kRunDefault];
+    const ListsIndex & X = A.ix;
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
     constexpr uint32_t kRun = kRunDefault;
     const uint64_t vt = A.hdr->vtotal;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, vt);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRun, vt);
     const uint32_t t = R.t, wv = R.wv;
     const uint64_t first = R.first;
     if (first >= vt)
@@ -232,17 +229,14 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
         return; // a run of tails only
     }
 
-    // ---- the selection of every unit: heads inside the run, the search before it
-    const uint32_t r0 = rl(r, 0) & kRecList;
-    const uint32_t k0 = r0 != 0u ? r0 - 1u : find_list(A.vbase, static_cast<uint32_t>(A.nsel), static_cast<uint32_t>(first), t);
-    const uint32_t id = umax32(wave_incl_max(r & kRecList), k0 + 1u) - 1u;
+    const uint32_t id = run_ids(r, A.vbase, A.nsel, first, t); // the selection of every unit
     const uint32_t vb = valid ? A.vbase[id] : 0u;
     const uint32_t lj = valid ? A.sel[id] : 0u;
     const uint32_t inl = static_cast<uint32_t>(v) - vb; // unit v - vb of its list
     // the source unit: the plan checked sel[k] < nlists and list_unit[j] + units_j <= nunits
-    const uint32_t su = full ? A.list_unit[lj] + inl : 0u;
-    const uint64_t o = full ? A.off[su] : 0ull;
-    const uint64_t e = full ? A.off[su + 1u] : 0ull;
+    const uint32_t su = full ? X.list_unit[lj] + inl : 0u;
+    const uint64_t o = full ? X.off[su] : 0ull;
+    const uint64_t e = full ? X.off[su + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
     P.init(R.in_base, R.in_end, o, e, full);
     if (!SUM && t < kRun)
@@ -251,22 +245,18 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
     // (the output plane's gathers depend on the selection only, like the
     // offsets': they are settled before the chunks go in flight, which keeps
     // the delta-1 form inside the registers of 7 waves per SIMD)
-    uint32_t rel = 0u, startv = 0u, sumv = 0u;
-    __amdgpu_buffer_rsrc_t ors = make_rsrc(A.out, 0u);
+    uint32_t startv = 0u, sumv = 0u;
+    RunOut O;
     if constexpr (!SUM)
     {
-        const uint64_t opos = (valid ? A.out_ptr[id] : 0ull) + 256ull * inl;
-        const uint64_t opos0 = readlane_u64(opos, 0);
-        rel = static_cast<uint32_t>(opos - opos0) * 4u; // bytes from the run's first value
-        const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
-        ors = make_rsrc(A.out + opos0, rl(rel, lastf) + 1024u);
+        O = RunOut(A.out, (valid ? A.out_ptr[id] : 0ull) + 256ull * inl, fullmask);
         if constexpr (D1)
         {
             // start0[list] + P(v) - P(vbase[k]) mod 2^32, P = the prefix of the
             // block sums over the virtual units (tails count 0)
             const uint32_t sv = valid ? A.sums[v] : 0u;
             const uint32_t pu = run_base(A.run_pre, A.run_tile, first / kRun) + wave_incl_scan(sv) - sv;
-            const uint32_t s0 = (valid && A.start0 != nullptr) ? A.start0[lj] : 0u;
+            const uint32_t s0 = (valid && X.start0 != nullptr) ? X.start0[lj] : 0u;
             startv = valid ? s0 + pu - A.pbase[id] : 0u;
         }
     }
@@ -285,7 +275,7 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
             sumv = t == jj ? sm : sumv;
         }
         else
-            st16_run(ors, rl(rel, jj) + 16u * t, x);
+            O.store(jj, t, x);
         wave_lds_sync();
     });
     if constexpr (SUM)
@@ -300,24 +290,25 @@ __global__ __launch_bounds__(256, MINW) void k_sel_dec(const SelArgs A)
         report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
 }
 
-// Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
-// decoder's pipeline, as k_lists_tails does for the lists of a stream; lane t
-// holds selection first + t's tail unit -- source unit list_unit[sel[k]] +
-// n / 256 of n % 256 values at the end of the selection's output -- or
-// nothing.  Delta-1: the tail starts at start0 + P(vbase[k + 1]) - P(vbase[k]).
+// Tails: every wave owns kRunDefault consecutive SELECTIONS through the tails
+// driver (tail_units, p4_lists_dev.h), as k_lists_tails does for the lists of
+// a stream; lane t holds selection first + t's tail unit -- source unit
+// list_unit[sel[k]] + n / 256 of n % 256 values at the end of the selection's
+// output -- or nothing.  Delta-1: the tail starts at start0 + P(vbase[k + 1])
+// - P(vbase[k]).
 // (A kernel of its own for the reason recorded above k_lists_tails.)
 template <bool D1, uint32_t NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sel_tails(const SelArgs A)
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
     __shared__ uint32_t scratch[4][kListScratchU32];
+    const ListsIndex & X = A.ix;
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nsel);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRunDefault, A.nsel);
     const uint32_t t = R.t;
     if (R.first >= A.nsel)
         return;
-    uint32_t * slot = slots[R.wv];
     const uint64_t k = R.first + t;
     const uint64_t p0 = t < R.n ? A.out_ptr[k] : 0ull;
     const uint64_t p1 = t < R.n ? A.out_ptr[k + 1u] : 0ull;
@@ -327,32 +318,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_se
     if (hasmask == 0ull)
         return;
     const uint32_t lj = has ? A.sel[k] : 0u;
-    const uint32_t su = has ? A.list_unit[lj] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
-    const uint64_t o = has ? A.off[su] : 0ull;
-    const uint64_t e = has ? A.off[su + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
+    const uint32_t su = has ? X.list_unit[lj] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
     const uint64_t opos = p1 - cnt;
-    uint32_t startv = 0u;
-    if constexpr (D1)
-        startv = has ? (A.start0 != nullptr ? A.start0[lj] : 0u) + A.pbase[k + 1u] - A.pbase[k] : 0u;
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals x;
-        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
-        uint32_t * op = A.out + readlane_u64(opos, jj);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            if (t + 64u * q < cj)
-                __builtin_nontemporal_store(x.v[q], op + t + 64u * q);
-        wave_lds_sync();
-    });
-    report_bad_units(A.err, badmask, su, t);
+    tail_units<D1, NC>(
+        R, X.off, has, hasmask, su, cnt, slots[R.wv], scratch[R.wv], A.err,
+        [&] { return D1 && has ? (X.start0 != nullptr ? X.start0[lj] : 0u) + A.pbase[k + 1u] - A.pbase[k] : 0u; },
+        tail_store<true>(A.out, opos, t));
 }
 
 } // namespace tpf::dev
@@ -398,13 +369,11 @@ hipError_t launch_lists_unit_base(const uint64_t * ptr, uint64_t nlists, uint32_
     hipError_t e = fill_u32(hdr, 0xFFFFFFFFu, 4, s);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_unit_base_plan, dim3(flat_grid(nlists, s)), dim3(256), 0, s, ptr, nlists, scan.tot, hdr);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_unit_base_plan, flat_grid(nlists, s), 256, s, ptr, nlists, scan.tot, hdr)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u64(scan.tot, nlists, scan.pre, scan.tile, reinterpret_cast<uint64_t *>(hdr + 1), s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_unit_base_write, dim3(flat_grid(nlists, s)), dim3(256), 0, s, nlists, scan.pre, scan.tile, hdr, list_unit, err);
-    return hipGetLastError();
+    return launch(dev::k_unit_base_write, flat_grid(nlists, s), 256, s, nlists, scan.pre, scan.tile, hdr, list_unit, err);
 }
 
 uint64_t lists_select_unit_cap(uint64_t nsel, uint64_t out_values) { return out_values / 256u + nsel; }
@@ -423,59 +392,61 @@ hipError_t launch_sel_heads(uint64_t nsel, uint64_t nunits, uint64_t out_values,
         return e;
     if ((e = launch_run_scan_u64t(totv, nsel, prev, tilev, reinterpret_cast<uint64_t *>(&hdr->ototal), s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_sel_heads, dim3(flat_grid(nsel, s)), dim3(256), 0, s, nsel, nunits, out_values, vcap, scanu.tot, totv,
-                       scanu.pre, scanu.tile, prev, tilev, hdr, vbase, rec, out_ptr, err);
-    return hipGetLastError();
+    return launch(dev::k_sel_heads, flat_grid(nsel, s), 256, s, nsel, nunits, out_values, vcap, scanu.tot, totv, scanu.pre, scanu.tile, prev,
+                  tilev, hdr, vbase, rec, out_ptr, err);
 }
 
-hipError_t launch_lists_select(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                               const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * sel,
-                               uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
-                               hipStream_t s)
+hipError_t launch_lists_select(const ListsIndex & X, bool d1, const uint32_t * sel, uint64_t nsel, uint32_t * out, uint64_t out_values,
+                               uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s)
 {
     if (nsel == 0)
         return out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess;
     const uint64_t vcap = lists_select_unit_cap(nsel, out_values);
-    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull)
+    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || X.nlists > 0x7FFFFFFFull || X.nunits > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const SelWs W(ws, nsel, vcap);
     const SelPlanWs & S = W.plan;
     hipError_t e = fill_u32(S.hdr, 0xFFFFFFFFu, 2, s);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_sel_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, nsel,
-                       S.scanu.tot, S.totv, S.hdr, W.rec, vcap);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    if ((e = launch_sel_heads(nsel, nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+    if ((e = launch(dev::k_sel_plan, flat_grid(std::max(nsel, vcap), s), 256, s, X.ptr, X.list_unit, X.nlists, X.nunits, sel, nsel, S.scanu.tot,
+                    S.totv, S.hdr, W.rec, vcap))
         != hipSuccess)
         return e;
-    const dev::SelArgs A{in, in_bytes, off, list_unit, start0, sel, nsel, out, out_values, vcap, out_ptr, S.hdr, W.rec, S.vbase, W.pbase,
-                         W.sums, W.scans.tot, W.scans.pre, W.scans.tile, err};
+    if ((e = launch_sel_heads(nsel, X.nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+        != hipSuccess)
+        return e;
+    const dev::SelArgs A{.ix = X,
+                         .sel = sel,
+                         .nsel = nsel,
+                         .out = out,
+                         .out_values = out_values,
+                         .vcap = vcap,
+                         .out_ptr = out_ptr,
+                         .hdr = S.hdr,
+                         .rec = W.rec,
+                         .vbase = S.vbase,
+                         .pbase = W.pbase,
+                         .sums = W.sums,
+                         .run_tot = W.scans.tot,
+                         .run_pre = W.scans.pre,
+                         .run_tile = W.scans.tile,
+                         .err = err};
     // sized by the host's cap: waves past the real unit count exit
-    const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    const uint32_t tgrid = static_cast<uint32_t>((nsel + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    if (!d1)
+    const uint32_t grid = wave_grid(vcap, dev::kRunDefault), tgrid = wave_grid(nsel, dev::kRunDefault);
+    if (d1)
     {
-        hipLaunchKernelGGL((dev::k_sel_dec<false, dev::kListsNC, dev::kListsMinW, false>), dim3(grid), dim3(256), 0, s, A);
-        if ((e = hipGetLastError()) != hipSuccess)
+        // the block sums of the virtual units, their run scan, one prefix per selection
+        if ((e = launch(dev::k_sel_dec<false, dev::kListsNC, dev::kListsMinW, true>, grid, 256, s, A)) != hipSuccess)
             return e;
-        hipLaunchKernelGGL((dev::k_sel_tails<false, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-        return hipGetLastError();
+        if ((e = launch_run_scan_u32(W.scans.tot, sel_runs(vcap), W.scans.pre, W.scans.tile, nullptr, s)) != hipSuccess)
+            return e;
+        if ((e = launch(dev::k_sel_pbase, flat_grid(nsel + 1u, s), 256, s, A, W.pbase)) != hipSuccess)
+            return e;
     }
-    hipLaunchKernelGGL((dev::k_sel_dec<false, dev::kListsNC, dev::kListsMinW, true>), dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_sel_dec<D1, dev::kListsNC, dev::kListsMinW, false>; }, grid, 256, s, A)) != hipSuccess)
         return e;
-    if ((e = launch_run_scan_u32(W.scans.tot, sel_runs(vcap), W.scans.pre, W.scans.tile, nullptr, s)) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(dev::k_sel_pbase, dim3(flat_grid(nsel + 1u, s)), dim3(256), 0, s, A, W.pbase);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_sel_dec<true, dev::kListsNC, dev::kListsMinW, false>), dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((dev::k_sel_tails<true, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    return hipGetLastError();
+    return launch_by(d1, [](auto D1) { return dev::k_sel_tails<D1, dev::kTailsNC>; }, tgrid, 256, s, A);
 }
 
 } // namespace tpf

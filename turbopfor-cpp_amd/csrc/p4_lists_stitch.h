@@ -79,18 +79,19 @@ __device__ __forceinline__ void wave_move(uint8_t * dst, const uint8_t * src, ui
         dst[tail0 + (t - head)] = src[tail0 + (t - head)];
 }
 
-// A wave's tile of the output.  Args (AppArgs, RemArgs) names, per list j of n:
-// lstart[j] (n + 1) its first output byte, kbpre[j] (n + 1) the kept bytes of
-// the lists before it, its kept bytes at in + off[lunit[j]], its new bytes at
-// sbytes + noff[subase[j]]; hdr->go and hdr->fit gate the pass.
+// A wave's tile of the output, n lists.  Args (AppArgs, RemArgs) names the old
+// index ix and, per list j of the result: lstart[j] (n + 1) its first output
+// byte, kbpre[j] (n + 1) the kept bytes of the lists before it, its kept bytes
+// at ix.in + ix.off[ix.list_unit[j]], its new bytes at sbytes +
+// noff[subase[j]]; hdr->go and hdr->fit gate the pass.
 template <class Args>
-__device__ __forceinline__ void stitch_tile(const Args & A)
+__device__ __forceinline__ void stitch_tile(const Args & A, uint64_t nlists_out)
 {
     if (A.hdr->go == 0u || A.hdr->fit == 0u)
         return;
     const uint32_t t = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
-    const uint32_t n = static_cast<uint32_t>(A.n);
+    const uint32_t n = static_cast<uint32_t>(nlists_out);
     const uint64_t total = A.lstart[n];
     const uint64_t x0 = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kListsAppendTile;
     if (x0 >= total)
@@ -110,7 +111,7 @@ __device__ __forceinline__ void stitch_tile(const Args & A)
         {
             kb = A.kbpre[j + 1u] - A.kbpre[j];
             if (kb != 0ull)
-                ksrc = reinterpret_cast<uint64_t>(A.in) + A.off[A.lunit[j]];
+                ksrc = reinterpret_cast<uint64_t>(A.ix.in) + A.ix.off[A.ix.list_unit[j]];
             nsrc = reinterpret_cast<uint64_t>(A.sbytes) + A.noff[A.subase[j]];
         }
         // a list of at most kAppLaneBytes bytes inside the tile is moved by its own lane, 64 lists at a time: a tile of

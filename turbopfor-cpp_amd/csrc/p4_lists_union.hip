@@ -8,11 +8,12 @@
 // at position p goes p + (the misses with L <= p) slots in.  L comes from the
 // intersection's lookup (p4_lists_intersect.hip, its EVERY form): every probe
 // value's unit is decoded once into LDS and searched.  The list values come
-// from k_un_dec's and k_un_tails's pipelines (p4_lists_units.hip) over the
-// virtual units of the targeted lists, every unit decoded once from the skip
-// table; the shift of each of a unit's 256 values is a histogram of the misses
-// that land in the unit, in the wave's LDS, and its prefix sum.  No decoded
-// value is staged in global memory, and nothing is sized by the index.
+// from k_un_dec's pipeline (p4_lists_units.hip) and the tails driver
+// (p4_lists_dev.h) over the virtual units of the targeted lists, every unit
+// decoded once from the skip table; the shift of each of a unit's 256 values
+// is a histogram of the misses that land in the unit, in the wave's LDS, and
+// its prefix sum.  No decoded value is staged in global memory, and nothing is
+// sized by the index.
 #include "p4_lists.h"
 
 #include "p4_dec256v32.h"
@@ -42,15 +43,7 @@ struct UoHdr
 
 struct UoArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * ptr;
-    const uint32_t * list_unit;
-    uint64_t nlists;
-    const uint32_t * start0;
-    const uint32_t * unit_last;
+    ListsIndex ix;
     const uint32_t * probe;
     uint64_t pv;
     const uint64_t * probe_ptr;
@@ -160,8 +153,8 @@ __global__ __launch_bounds__(256) void k_uo_plan(const UoArgs A)
         if (go)
         {
             const uint32_t j = A.qlist[k];
-            units = A.list_unit[j + 1u] - A.list_unit[j];
-            nv = A.ptr[j + 1u] - A.ptr[j] + (uo_prefix(A, A.probe_ptr[k + 1u]) - mb);
+            units = A.ix.list_unit[j + 1u] - A.ix.list_unit[j];
+            nv = A.ix.ptr[j + 1u] - A.ix.ptr[j] + (uo_prefix(A, A.probe_ptr[k + 1u]) - mb);
         }
         A.totu[k] = units;
         A.totv[k] = nv;
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(256) void k_uo_heads(const UoArgs A)
     if (!items_go(A.hdr))
     {
         if (gid == 0 && A.err != nullptr)
-            *A.err = A.nunits + A.hdr->bad;
+            *A.err = A.ix.nunits + A.hdr->bad;
         return;
     }
     const bool go = uo_go(A);
@@ -191,7 +184,7 @@ __global__ __launch_bounds__(256) void k_uo_heads(const UoArgs A)
     {
         A.out_ptr[A.nq] = A.uh->ototal;
         if (!go && A.err != nullptr)
-            atomicMin(A.err, static_cast<unsigned long long>(A.nunits + A.nq));
+            atomicMin(A.err, static_cast<unsigned long long>(A.ix.nunits + A.nq));
     }
     if (!go)
         return;
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(256) void k_uo_heads(const UoArgs A)
         A.vbase[k] = vb;
         const uint32_t units = A.totu[k];
         const uint32_t j = A.qlist[k];
-        const bool tail = ((A.ptr[j + 1u] - A.ptr[j]) & 255u) != 0u;
+        const bool tail = ((A.ix.ptr[j + 1u] - A.ix.ptr[j]) & 255u) != 0u;
         if (units == 1u)
             A.rec[vb] = static_cast<uint32_t>(k + 1u) | (tail ? kRecTail : 0u);
         else if (units != 0u)
@@ -219,10 +212,10 @@ __global__ __launch_bounds__(256) void k_uo_heads(const UoArgs A)
 // else the unit's first position plus q, held to n_j.
 __device__ __forceinline__ uint32_t uo_pos(const UoArgs & A, uint64_t i, uint32_t r, uint32_t j)
 {
-    const uint64_t n = A.ptr[j + 1u] - A.ptr[j];
+    const uint64_t n = A.ix.ptr[j + 1u] - A.ix.ptr[j];
     uint64_t l = n;
     if ((r & kUoNone) == 0u)
-        l = min_u64(256ull * ((A.pu[i] & kRecList) - A.list_unit[j]) + (r & kIxQ), n);
+        l = min_u64(256ull * ((A.pu[i] & kRecList) - A.ix.list_unit[j]) + (r & kIxQ), n);
     return static_cast<uint32_t>(l);
 }
 
@@ -388,7 +381,7 @@ __global__ __launch_bounds__(256, MINW) void k_uo_dec(const UoArgs A)
         return;
     constexpr uint32_t kRun = RUN;
     const uint64_t vt = A.uh->vtotal;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, vt);
+    const WaveRun R = wave_run(A.ix.in, A.ix.in_bytes, kRun, vt);
     const uint32_t t = R.t, wv = R.wv;
     const uint64_t first = R.first;
     if (first >= vt)
@@ -403,23 +396,20 @@ __global__ __launch_bounds__(256, MINW) void k_uo_dec(const UoArgs A)
     if (fullmask == 0ull)
         return; // a run of tails only
 
-    // ---- the query of every unit: heads inside the run, the search before it
-    const uint32_t r0 = rl(r, 0) & kRecList;
-    const uint32_t k0 = r0 != 0u ? r0 - 1u : find_list(A.vbase, static_cast<uint32_t>(A.nq), static_cast<uint32_t>(first), t);
-    const uint32_t id = umax32(wave_incl_max(r & kRecList), k0 + 1u) - 1u;
+    const uint32_t id = run_ids(r, A.vbase, A.nq, first, t); // the query of every unit
     const uint32_t vb = valid ? A.vbase[id] : 0u;
     const uint32_t lj = valid ? A.qlist[id] : 0u;
     const uint32_t inl = static_cast<uint32_t>(v) - vb; // unit v - vb of its list
     // the source unit: the plan checked qlist[k] < nlists and list_unit[j] + units_j <= nunits
-    const uint32_t su = full ? A.list_unit[lj] + inl : 0u;
-    const uint64_t o = full ? A.off[su] : 0ull;
-    const uint64_t e = full ? A.off[su + 1u] : 0ull;
+    const uint32_t su = full ? A.ix.list_unit[lj] + inl : 0u;
+    const uint64_t o = full ? A.ix.off[su] : 0ull;
+    const uint64_t e = full ? A.ix.off[su + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
     P.init(R.in_base, R.in_end, o, e, full);
     if (t < kRun)
     {
         srcu[wv][t] = full ? su : 0xFFFFFFFFu;
-        starts[wv][t] = full ? unit_start(A.list_unit, A.start0, A.unit_last, lj, su) : 0u;
+        starts[wv][t] = full ? unit_start(A.ix.list_unit, A.ix.start0, A.ix.unit_last, lj, su) : 0u;
         if (full)
             uo_unit_plan(A, id, inl, 256ull * inl + 256u, units[wv][t]);
     }
@@ -442,10 +432,11 @@ __global__ __launch_bounds__(256, MINW) void k_uo_dec(const UoArgs A)
     report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
 }
 
-// Tails: every wave owns kRunDefault consecutive QUERIES with the generic
-// decoder's pipeline, as k_un_tails does for selections; lane t holds query
-// first + t's tail unit -- the list's last unit, n % 256 values -- or nothing.
-// Lane t holds positions t + 64q of the unit, as uo_write_unit takes them.
+// Tails: every wave owns kRunDefault consecutive QUERIES through the tails
+// driver (tail_units, p4_lists_dev.h), as k_un_tails does for selections; lane
+// t holds query first + t's tail unit -- the list's last unit, n % 256 values
+// -- or nothing.  Lane t holds positions t + 64q of the unit, as uo_write_unit
+// takes them.
 template <uint32_t NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_uo_tails(const UoArgs A)
 {
@@ -455,45 +446,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_uo
     __shared__ UoUnit units[4][kRunDefault];
     if (!uo_go(A))
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nq);
+    const WaveRun R = wave_run(A.ix.in, A.ix.in_bytes, kRunDefault, A.nq);
     const uint32_t t = R.t, wv = R.wv;
     if (R.first >= A.nq)
         return;
-    uint32_t * slot = slots[wv];
     const uint64_t k = R.first + t;
     const uint32_t lj = t < R.n ? A.qlist[k] : 0u;
-    const uint64_t n = t < R.n ? A.ptr[lj + 1u] - A.ptr[lj] : 0ull;
+    const uint64_t n = t < R.n ? A.ix.ptr[lj + 1u] - A.ix.ptr[lj] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>(n & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
     if (hasmask == 0ull)
         return;
     const uint32_t inl = static_cast<uint32_t>(n >> 8);
-    const uint32_t su = has ? A.list_unit[lj] + inl : 0u; // the list's last unit: the plan checked the unit count
-    const uint64_t o = has ? A.off[su] : 0ull;
-    const uint64_t e = has ? A.off[su + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
-    uint32_t startv = 0u;
-    if (has)
-    {
-        startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
-        uo_unit_plan(A, static_cast<uint32_t>(k), inl, n, units[wv][t]); // a miss with L = n shifts no list value
-    }
-    wave_lds_sync();
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals x;
-        decode_tail_unit<true>(P, c, jj, slot, scratch[wv], cj, rl(startv, jj), t, x, badmask);
-        uo_write_unit(A, units[wv][jj], hist[wv], cj, t, x.v);
-        wave_lds_sync();
-    });
-    report_bad_units(A.err, badmask, su, t);
+    const uint32_t su = has ? A.ix.list_unit[lj] + inl : 0u; // the list's last unit: the plan checked the unit count
+    tail_units<true, NC>(
+        R, A.ix.off, has, hasmask, su, cnt, slots[wv], scratch[wv], A.err,
+        [&] {
+            // with the start, behind the offsets' loads: the plan of every lane's unit, which waits in LDS
+            uint32_t startv = 0u;
+            if (has)
+            {
+                startv = unit_start(A.ix.list_unit, A.ix.start0, A.ix.unit_last, lj, su);
+                uo_unit_plan(A, static_cast<uint32_t>(k), inl, n, units[wv][t]); // a miss with L = n shifts no list value
+            }
+            wave_lds_sync();
+            return startv;
+        },
+        [&](uint32_t jj, uint32_t cj, const TailVals & x) { uo_write_unit(A, units[wv][jj], hist[wv], cj, t, x.v); });
 }
 
 } // namespace tpf::dev
@@ -547,10 +527,8 @@ size_t lists_union_workspace(uint64_t nq, uint64_t probe_values, uint64_t out_va
     return UoWs(nullptr, nq, probe_values, lists_select_unit_cap(nq, out_values)).bytes;
 }
 
-hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                              const uint32_t * list_unit, uint64_t nlists, const uint32_t * start0, const uint32_t * unit_last,
-                              const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist, uint64_t nq,
-                              uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx, uint32_t * out_tpos,
+hipError_t launch_lists_union(const ListsIndex & X, const uint32_t * probe, uint64_t pv, const uint64_t * probe_ptr, const uint32_t * qlist,
+                              uint64_t nq, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, uint32_t * out_pidx, uint32_t * out_tpos,
                               void * ws, unsigned long long * err, hipStream_t s)
 {
     if (nq == 0)
@@ -559,63 +537,79 @@ hipError_t launch_lists_union(const uint8_t * in, uint64_t in_bytes, const uint6
         return e != hipSuccess ? e : (out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess);
     }
     const uint64_t vcap = lists_select_unit_cap(nq, out_values);
-    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull)
+    if (nq > 0x7FFFFFFFull || pv > 0x7FFFFFFFull || X.nlists > 0x7FFFFFFFull || X.nunits > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const UoWs W(ws, nq, pv, vcap);
     const uint64_t nruns = (pv + 63u) / 64u;
     // one wave per 64 probe indices, per kUoRun virtual units, per kRunDefault queries: at least one workgroup for an empty probe
     const uint32_t rgrid = static_cast<uint32_t>(std::max<uint64_t>(1, (nruns + 3u) / 4u));
-    const uint32_t vgrid = static_cast<uint32_t>((vcap + 4u * dev::kUoRun - 1u) / (4u * dev::kUoRun));
-    const uint32_t tgrid = static_cast<uint32_t>((nq + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
+    const uint32_t vgrid = wave_grid(vcap, dev::kUoRun), tgrid = wave_grid(nq, dev::kRunDefault);
     const uint32_t pgrid = flat_grid(pv, s);
     hipError_t e = launch_items_reset(err, W.hdr, s);
     if (e != hipSuccess)
         return e;
     // ---- the lookup: the intersection's plan, items and decode, every probe value's q recorded
-    if ((e = launch_ix_plan(ptr, list_unit, nlists, nunits, unit_last, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
+    if ((e = launch_ix_plan(X, probe, pv, probe_ptr, qlist, nq, W.hdr, W.pu, W.pl, s)) != hipSuccess)
         return e;
     if ((e = launch_items(pv, W.hdr, W.pu, W.pl, W.scani, W.ihead, W.iend, W.res, s)) != hipSuccess)
         return e;
-    const dev::IxArgs X{in, in_bytes, off, nunits, ptr, list_unit, start0, unit_last, probe, pv, W.hdr, W.pu, W.pl, W.ihead, W.iend,
-                        W.res, err};
-    if ((e = launch_ix_lookup(X, true, s)) != hipSuccess)
+    const dev::IxArgs L{.it = {.ix = X, .hdr = W.hdr, .pu = W.pu, .pl = W.pl, .ihead = W.ihead, .iend = W.iend, .err = err},
+                        .probe = probe,
+                        .pv = pv,
+                        .res = W.res};
+    if ((e = launch_ix_lookup(L, true, s)) != hipSuccess)
         return e;
     // ---- the misses, the sizes, the verdict
-    const dev::UoArgs A{in,        in_bytes,  off,          nunits,      ptr,          list_unit,    nlists,     start0,  unit_last, probe,
-                        pv,        probe_ptr, qlist,        nq,          out,          out_values,   vcap,       out_ptr, out_pidx,  out_tpos,
-                        W.hdr,     W.uh,      W.pu,         W.res,       W.scanm.tot,  W.scanm.pre,  W.scanm.tile, W.missbase, W.mlb,
-                        W.scanu.tot, W.totv,  W.scanu.pre,  W.scanu.tile, W.prev,      W.tilev,      W.vbase,    W.rec,   err};
-    hipLaunchKernelGGL(dev::k_uo_flags, dim3(rgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    const dev::UoArgs A{.ix = X,
+                        .probe = probe,
+                        .pv = pv,
+                        .probe_ptr = probe_ptr,
+                        .qlist = qlist,
+                        .nq = nq,
+                        .out = out,
+                        .out_values = out_values,
+                        .vcap = vcap,
+                        .out_ptr = out_ptr,
+                        .out_pidx = out_pidx,
+                        .out_tpos = out_tpos,
+                        .hdr = W.hdr,
+                        .uh = W.uh,
+                        .pu = W.pu,
+                        .res = W.res,
+                        .mtot = W.scanm.tot,
+                        .mpre = W.scanm.pre,
+                        .mtile = W.scanm.tile,
+                        .missbase = W.missbase,
+                        .mlb = W.mlb,
+                        .totu = W.scanu.tot,
+                        .totv = W.totv,
+                        .preu = W.scanu.pre,
+                        .tileu = W.scanu.tile,
+                        .prev = W.prev,
+                        .tilev = W.tilev,
+                        .vbase = W.vbase,
+                        .rec = W.rec,
+                        .err = err};
+    if ((e = launch(dev::k_uo_flags, rgrid, 256, s, A)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u32_single(W.scanm.tot, nruns, W.scanm.pre, W.scanm.tile, &W.hdr->spare, s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_uo_plan, dim3(flat_grid(std::max(nq + 1u, vcap), s)), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_uo_plan, flat_grid(std::max(nq + 1u, vcap), s), 256, s, A)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u64(W.scanu.tot, nq, W.scanu.pre, W.scanu.tile, reinterpret_cast<uint64_t *>(&W.uh->vtotal), s)) != hipSuccess)
         return e;
     if ((e = launch_run_scan_u64t(W.totv, nq, W.prev, W.tilev, reinterpret_cast<uint64_t *>(&W.uh->ototal), s)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_uo_heads, dim3(flat_grid(nq, s)), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_uo_heads, flat_grid(nq, s), 256, s, A)) != hipSuccess)
         return e;
     // ---- the output: misses, list values, then the hits' probe indices over the list values' words
-    hipLaunchKernelGGL(dev::k_uo_probe<false>, dim3(pgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_uo_probe<false>, pgrid, 256, s, A)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL((dev::k_uo_dec<dev::kUoRun, dev::kUoNC, dev::kUoMinW>), dim3(vgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_uo_dec<dev::kUoRun, dev::kUoNC, dev::kUoMinW>, vgrid, 256, s, A)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL((dev::k_uo_tails<dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_uo_tails<dev::kTailsNC>, tgrid, 256, s, A)) != hipSuccess)
         return e;
-    if (out_pidx != nullptr)
-    {
-        hipLaunchKernelGGL(dev::k_uo_probe<true>, dim3(pgrid), dim3(256), 0, s, A);
-        e = hipGetLastError();
-    }
-    return e;
+    return out_pidx != nullptr ? launch(dev::k_uo_probe<true>, pgrid, 256, s, A) : hipSuccess;
 }
 
 } // namespace tpf

@@ -22,13 +22,7 @@ namespace tpf::dev
 // ---- the skip table ---------------------------------------------------------
 struct UlArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    uint64_t nunits;
-    const uint64_t * ptr;
-    uint64_t nlists;
-    const uint32_t * start0;
+    ListsIndex ix;             // (no unit directory, and the skip table is what is built)
     const ListsHdr * hdr;
     const uint32_t * rec;      // unit records (p4_lists.h)
     const uint32_t * ubase;    // first unit of every list
@@ -46,14 +40,14 @@ struct UlArgs
 // starts at nunits holds no unit: its entry is never read.)
 __global__ __launch_bounds__(256) void k_ul_pbase(const UlArgs A)
 {
-    if (!lists_go(A.hdr, A.nunits))
+    if (!lists_go(A.hdr, A.ix.nunits))
         return;
     const uint64_t gsz = static_cast<uint64_t>(gridDim.x) * 256u;
-    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; j < A.nlists; j += gsz)
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x; j < A.ix.nlists; j += gsz)
     {
         const uint32_t x = A.ubase[j];
         uint32_t acc = 0u;
-        if (x < A.nunits)
+        if (x < A.ix.nunits)
         {
             acc = run_base(A.run_pre, A.run_tile, x / kSumRun);
             for (uint32_t q = x / kSumRun * kSumRun; q < x; ++q)
@@ -63,82 +57,69 @@ __global__ __launch_bounds__(256) void k_ul_pbase(const UlArgs A)
     }
 }
 
-// The tails' sums: every wave owns kRunDefault consecutive LISTS with the
-// generic decoder's pipeline, as k_lists_tails does; lane t holds list first +
-// t's tail unit or nothing.  The decoded gaps are summed, not stored.
+// The tails' sums: every wave owns kRunDefault consecutive LISTS through the
+// tails driver (tail_units, p4_lists_dev.h), as k_lists_tails does; lane t
+// holds list first + t's tail unit or nothing.  The decoded gaps are summed,
+// not stored.
 template <uint32_t NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ul_tails(const UlArgs A)
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
     __shared__ uint32_t scratch[4][kListScratchU32];
-    if (!lists_go(A.hdr, A.nunits))
+    const ListsIndex & X = A.ix;
+    if (!lists_go(A.hdr, X.nunits))
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nlists);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRunDefault, X.nlists);
     const uint32_t t = R.t;
-    if (R.first >= A.nlists)
+    if (R.first >= X.nlists)
         return;
-    uint32_t * slot = slots[R.wv];
     const uint64_t j = R.first + t;
-    const uint64_t p0 = t < R.n ? A.ptr[j] : 0ull;
-    const uint64_t p1 = t < R.n ? A.ptr[j + 1u] : 0ull;
+    const uint64_t p0 = t < R.n ? X.ptr[j] : 0ull;
+    const uint64_t p1 = t < R.n ? X.ptr[j + 1u] : 0ull;
     const uint32_t cnt = static_cast<uint32_t>((p1 - p0) & 255u);
     const bool has = cnt != 0u;
     const uint64_t hasmask = __ballot(has);
     if (hasmask == 0ull)
         return;
     const uint32_t u = has ? A.ubase[j] + static_cast<uint32_t>((p1 - p0) >> 8) : 0u;
-    const uint64_t o = has ? A.off[u] : 0ull;
-    const uint64_t e = has ? A.off[u + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
     uint32_t sumv = 0u;
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals v;
-        decode_tail_unit<false>(P, c, jj, slot, scratch[R.wv], cj, 0u, t, v, badmask);
-        uint32_t loc = 0u;
+    tail_units<false, NC>(
+        R, X.off, has, hasmask, u, cnt, slots[R.wv], scratch[R.wv], A.err, [] { return 0u; },
+        [&](uint32_t jj, uint32_t cj, const TailVals & v) {
+            uint32_t loc = 0u;
 #pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            loc += t + 64u * q < cj ? v.v[q] + 1u : 0u;
-        const uint32_t sm = wave_sum(loc);
-        sumv = t == jj ? sm : sumv;
-        wave_lds_sync();
-    });
+            for (uint32_t q = 0; q < 4; ++q)
+                loc += t + 64u * q < cj ? v.v[q] + 1u : 0u;
+            const uint32_t sm = wave_sum(loc);
+            sumv = t == jj ? sm : sumv;
+        });
     if (has)
         A.tsum[j] = sumv;
-    report_bad_units(A.err, badmask, u, t);
 }
 
 // The write pass: every wave owns one of phase A's 64-unit runs, lane t unit
 // first + t.  last(u) = start0[list] + P(u + 1) - P(ubase[list]) mod 2^32, a
-// tail adding its own sum (phase A counts it 0); the list of every unit from
-// the head records inside the run and one search for the run's first unit.
+// tail adding its own sum (phase A counts it 0); the list of every unit by
+// run_ids (p4_lists_dev.h).
 __global__ __launch_bounds__(256) void k_ul_write(const UlArgs A)
 {
-    if (!lists_go(A.hdr, A.nunits))
+    if (!lists_go(A.hdr, A.ix.nunits))
         return;
     const uint32_t t = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kSumRun;
-    if (first >= A.nunits)
+    if (first >= A.ix.nunits)
         return;
-    const uint32_t n = static_cast<uint32_t>(min_u64(kSumRun, A.nunits - first));
+    const uint32_t n = static_cast<uint32_t>(min_u64(kSumRun, A.ix.nunits - first));
     const bool valid = t < n;
     const uint64_t u = first + t;
     const uint32_t r = valid ? A.rec[u] : 0u;
-    const uint32_t r0 = rl(r, 0) & kRecList;
-    const uint32_t j0 = r0 != 0u ? r0 - 1u : find_list(A.ubase, static_cast<uint32_t>(A.nlists), static_cast<uint32_t>(first), t);
-    const uint32_t id = umax32(wave_incl_max(r & kRecList), j0 + 1u) - 1u;
+    const uint32_t id = run_ids(r, A.ubase, A.ix.nlists, first, t);
     const uint32_t sv = valid ? A.sums[u] : 0u;
     const uint32_t p1 = run_base(A.run_pre, A.run_tile, first / kSumRun) + wave_incl_scan(sv);
     if (valid)
     {
-        const uint32_t s0 = A.start0 != nullptr ? A.start0[id] : 0u;
+        const uint32_t s0 = A.ix.start0 != nullptr ? A.ix.start0[id] : 0u;
         const uint32_t ts = (r & kRecTail) != 0u ? A.tsum[id] : 0u;
         A.unit_last[u] = s0 + p1 - A.pbase[id] + ts;
     }
@@ -206,12 +187,7 @@ __global__ __launch_bounds__(256) void k_range_units(const uint32_t * __restrict
 // ---- the decode of unit ranges -------------------------------------------------
 struct UnArgs
 {
-    const uint8_t * in;
-    uint64_t in_bytes;
-    const uint64_t * off;
-    const uint32_t * list_unit;
-    const uint32_t * start0;
-    const uint32_t * unit_last; // delta-1: the skip table (values, never indices)
+    ListsIndex ix;
     const uint32_t * sel;
     const uint32_t * ufirst;
     const uint32_t * ucount;
@@ -282,11 +258,12 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
     // the run's source units, for the error report only (k_sel_dec: held in a
     // register across the pipeline they cost spilled VGPRs at 7 waves)
     __shared__ uint32_t srcu[4][kRunDefault];
+    const ListsIndex & X = A.ix;
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
     constexpr uint32_t kRun = kRunDefault;
     const uint64_t vt = A.hdr->vtotal;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRun, vt);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRun, vt);
     const uint32_t t = R.t, wv = R.wv;
     const uint64_t first = R.first;
     if (first >= vt)
@@ -301,33 +278,26 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
     if (fullmask == 0ull)
         return; // a run of tails only
 
-    // ---- the selection of every unit: heads inside the run, the search before it
-    const uint32_t r0 = rl(r, 0) & kRecList;
-    const uint32_t k0 = r0 != 0u ? r0 - 1u : find_list(A.vbase, static_cast<uint32_t>(A.nsel), static_cast<uint32_t>(first), t);
-    const uint32_t id = umax32(wave_incl_max(r & kRecList), k0 + 1u) - 1u;
+    const uint32_t id = run_ids(r, A.vbase, A.nsel, first, t); // the selection of every unit
     const uint32_t vb = valid ? A.vbase[id] : 0u;
     const uint32_t lj = valid ? A.sel[id] : 0u;
     const uint32_t inl = static_cast<uint32_t>(v) - vb;          // unit v - vb of its range
     const uint32_t inu = (valid ? A.ufirst[id] : 0u) + inl;      // ... and unit inu of its list
     // the source unit: the plan checked sel[k] < nlists, ufirst + ucount <= units_j and list_unit[j] + units_j <= nunits
-    const uint32_t su = full ? A.list_unit[lj] + inu : 0u;
-    const uint64_t o = full ? A.off[su] : 0ull;
-    const uint64_t e = full ? A.off[su + 1u] : 0ull;
+    const uint32_t su = full ? X.list_unit[lj] + inu : 0u;
+    const uint64_t o = full ? X.off[su] : 0ull;
+    const uint64_t e = full ? X.off[su + 1u] : 0ull;
     RunPlaneT<kSlotBytes, true> P;
     P.init(R.in_base, R.in_end, o, e, full);
     if (t < kRun)
         srcu[wv][t] = full ? su : 0xFFFFFFFFu;
 
-    const uint64_t opos = (valid ? A.out_ptr[id] : 0ull) + 256ull * inl;
-    const uint64_t opos0 = readlane_u64(opos, 0);
-    const uint32_t rel = static_cast<uint32_t>(opos - opos0) * 4u; // bytes from the run's first value
-    const uint32_t lastf = 63u - static_cast<uint32_t>(__builtin_clzll(fullmask));
-    const __amdgpu_buffer_rsrc_t ors = make_rsrc(A.out + opos0, rl(rel, lastf) + 1024u);
+    const RunOut O(A.out, (valid ? A.out_ptr[id] : 0ull) + 256ull * inl, fullmask);
     uint32_t startv = 0u;
     if constexpr (D1)
     {
         if (full)
-            startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
+            startv = unit_start(X.list_unit, X.start0, X.unit_last, lj, su);
     }
     Chunk C[NC];
     pipe_prime<NC>(P, C, t);
@@ -338,29 +308,30 @@ __global__ __launch_bounds__(256, MINW) void k_un_dec(const UnArgs A)
             return;
         u32x4 x;
         decode_full_unit<D1>(P, c, jj, slot, scr, rl(startv, jj), t, x, badmask);
-        st16_run(ors, rl(rel, jj) + 16u * t, x);
+        O.store(jj, t, x);
         wave_lds_sync();
     });
     report_bad_units(A.err, badmask, t < kRun ? srcu[wv][t] : 0xFFFFFFFFu, t);
 }
 
-// Tails: every wave owns kRunDefault consecutive SELECTIONS with the generic
-// decoder's pipeline, as k_sel_tails does; lane t holds selection first + t's
-// tail unit -- the last unit of its range, n % 256 values at the end of the
-// selection's output -- or nothing.  Delta-1: the tail starts from the last
-// value of the unit before it, or from start0 in a tail-only list.
+// Tails: every wave owns kRunDefault consecutive SELECTIONS through the tails
+// driver (tail_units, p4_lists_dev.h), as k_sel_tails does; lane t holds
+// selection first + t's tail unit -- the last unit of its range, n % 256
+// values at the end of the selection's output -- or nothing.  Delta-1: the
+// tail starts from the last value of the unit before it, or from start0 in a
+// tail-only list.
 template <bool D1, uint32_t NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_un_tails(const UnArgs A)
 {
     __shared__ uint32_t slots[4][kListSlot / 4];
     __shared__ uint32_t scratch[4][kListScratchU32];
+    const ListsIndex & X = A.ix;
     if (!sel_go(A.hdr, A.out_values, A.vcap))
         return;
-    const WaveRun R = wave_run(A.in, A.in_bytes, kRunDefault, A.nsel);
+    const WaveRun R = wave_run(X.in, X.in_bytes, kRunDefault, A.nsel);
     const uint32_t t = R.t;
     if (R.first >= A.nsel)
         return;
-    uint32_t * slot = slots[R.wv];
     const uint64_t k = R.first + t;
     const uint64_t p0 = t < R.n ? A.out_ptr[k] : 0ull;
     const uint64_t p1 = t < R.n ? A.out_ptr[k + 1u] : 0ull;
@@ -371,35 +342,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_un
         return;
     const uint32_t lj = has ? A.sel[k] : 0u;
     const uint32_t inu = has ? A.ufirst[k] + A.ucount[k] - 1u : 0u; // the list's last unit (ucount >= 1)
-    const uint32_t su = has ? A.list_unit[lj] + inu : 0u;
-    const uint64_t o = has ? A.off[su] : 0ull;
-    const uint64_t e = has ? A.off[su + 1u] : 0ull;
-    RunPlaneT<kListSlot> P;
-    P.init(R.in_base, R.in_end, o, e, has);
+    const uint32_t su = has ? X.list_unit[lj] + inu : 0u;
     const uint64_t opos = p1 - cnt;
-    uint32_t startv = 0u;
-    if constexpr (D1)
-    {
-        if (has)
-            startv = unit_start(A.list_unit, A.start0, A.unit_last, lj, su);
-    }
-    uint64_t badmask = 0u;
-    Chunk C[NC];
-    pipe_prime<NC>(P, C, t);
-    pipe_drain<NC>(P, C, R.n, t, [&](const Chunk & c, uint32_t jj) {
-        if (((hasmask >> jj) & 1ull) == 0ull)
-            return;
-        const uint32_t cj = rl(cnt, jj);
-        TailVals x;
-        decode_tail_unit<D1>(P, c, jj, slot, scratch[R.wv], cj, rl(startv, jj), t, x, badmask);
-        uint32_t * op = A.out + readlane_u64(opos, jj);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            if (t + 64u * q < cj)
-                __builtin_nontemporal_store(x.v[q], op + t + 64u * q);
-        wave_lds_sync();
-    });
-    report_bad_units(A.err, badmask, su, t);
+    tail_units<D1, NC>(
+        R, X.off, has, hasmask, su, cnt, slots[R.wv], scratch[R.wv], A.err,
+        [&] { return D1 && has ? unit_start(X.list_unit, X.start0, X.unit_last, lj, su) : 0u; }, tail_store<true>(A.out, opos, t));
 }
 
 } // namespace tpf::dev
@@ -454,34 +401,37 @@ struct UnWs
 
 size_t lists_unit_last_workspace(uint64_t nunits, uint64_t nlists) { return UlWs(nullptr, nunits, nlists).bytes; }
 
-hipError_t launch_lists_unit_last(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                                  uint64_t nlists, const uint32_t * start0, uint32_t * unit_last, void * ws, unsigned long long * err,
-                                  hipStream_t s)
+hipError_t launch_lists_unit_last(const ListsIndex & X, uint32_t * unit_last, void * ws, unsigned long long * err, hipStream_t s)
 {
+    const uint64_t nunits = X.nunits, nlists = X.nlists;
     if (nunits == 0 || nlists == 0)
         return hipSuccess;
     if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const UlWs W(ws, nunits, nlists);
     // no value array to hold the pointers against: only their order is checked
-    hipError_t e = launch_lists_structure(ptr, nlists, ~0ull, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
+    hipError_t e = launch_lists_structure(X.ptr, nlists, ~0ull, nunits, W.hdr, W.scan, W.ubase, W.rec, err, s);
     if (e != hipSuccess)
         return e;
     ChainView cv;
-    if ((e = launch_lists_sums(in, in_bytes, off, nunits, W.rec, W.hdr, nlists, W.chain, &cv, err, s)) != hipSuccess)
+    if ((e = launch_lists_sums(X, W.rec, W.hdr, W.chain, &cv, err, s)) != hipSuccess)
         return e;
-    const dev::UlArgs A{in, in_bytes, off, nunits, ptr, nlists, start0, W.hdr, W.rec, W.ubase, cv.sums, cv.pre, cv.tile,
-                        W.pbase, W.tsum, unit_last, err};
-    hipLaunchKernelGGL(dev::k_ul_pbase, dim3(flat_grid(nlists, s)), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    const dev::UlArgs A{.ix = X,
+                        .hdr = W.hdr,
+                        .rec = W.rec,
+                        .ubase = W.ubase,
+                        .sums = cv.sums,
+                        .run_pre = cv.pre,
+                        .run_tile = cv.tile,
+                        .pbase = W.pbase,
+                        .tsum = W.tsum,
+                        .unit_last = unit_last,
+                        .err = err};
+    if ((e = launch(dev::k_ul_pbase, flat_grid(nlists, s), 256, s, A)) != hipSuccess)
         return e;
-    const uint32_t tgrid = static_cast<uint32_t>((nlists + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    hipLaunchKernelGGL((dev::k_ul_tails<dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch(dev::k_ul_tails<dev::kTailsNC>, wave_grid(nlists, dev::kRunDefault), 256, s, A)) != hipSuccess)
         return e;
-    const uint32_t wgrid = static_cast<uint32_t>((nunits + 4u * dev::kSumRun - 1u) / (4u * dev::kSumRun));
-    hipLaunchKernelGGL(dev::k_ul_write, dim3(wgrid), dim3(256), 0, s, A);
-    return hipGetLastError();
+    return launch(dev::k_ul_write, wave_grid(nunits, dev::kSumRun), 256, s, A);
 }
 
 hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t * unit_last, uint64_t nlists, uint64_t nunits,
@@ -490,9 +440,7 @@ hipError_t launch_lists_range_units(const uint32_t * list_unit, const uint32_t *
 {
     if (nq == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(dev::k_range_units, dim3(flat_grid(nq, s)), dim3(256), 0, s, list_unit, unit_last, nlists, nunits, qlist, qlo, qhi, nq,
-                       ufirst, ucount, err);
-    return hipGetLastError();
+    return launch(dev::k_range_units, flat_grid(nq, s), 256, s, list_unit, unit_last, nlists, nunits, qlist, qlo, qhi, nq, ufirst, ucount, err);
 }
 
 size_t lists_units_workspace(uint64_t nsel, uint64_t out_values)
@@ -500,44 +448,47 @@ size_t lists_units_workspace(uint64_t nsel, uint64_t out_values)
     return UnWs(nullptr, nsel, lists_select_unit_cap(nsel, out_values)).bytes;
 }
 
-hipError_t launch_lists_units(const uint8_t * in, uint64_t in_bytes, const uint64_t * off, uint64_t nunits, const uint64_t * ptr,
-                              const uint32_t * list_unit, uint64_t nlists, bool d1, const uint32_t * start0, const uint32_t * unit_last,
-                              const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount, uint64_t nsel, uint32_t * out,
-                              uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err, hipStream_t s)
+hipError_t launch_lists_units(const ListsIndex & X, bool d1, const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount,
+                              uint64_t nsel, uint32_t * out, uint64_t out_values, uint64_t * out_ptr, void * ws, unsigned long long * err,
+                              hipStream_t s)
 {
     if (nsel == 0)
         return out_ptr ? fill_u32(out_ptr, 0u, 2, s) : hipSuccess;
     const uint64_t vcap = lists_select_unit_cap(nsel, out_values);
-    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || (d1 && unit_last == nullptr))
+    if (nsel > 0x7FFFFFFFull || vcap > 0x7FFFFFFFull || X.nlists > 0x7FFFFFFFull || X.nunits > 0x7FFFFFFFull
+        || (d1 && X.unit_last == nullptr))
         return hipErrorInvalidValue;
     const UnWs W(ws, nsel, vcap);
     const SelPlanWs & S = W.plan;
     hipError_t e = fill_u32(S.hdr, 0xFFFFFFFFu, 2, s);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(dev::k_un_plan, dim3(flat_grid(std::max(nsel, vcap), s)), dim3(256), 0, s, ptr, list_unit, nlists, nunits, sel, ufirst,
-                       ucount, nsel, S.scanu.tot, S.totv, S.hdr, W.rec, vcap);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return e;
-    if ((e = launch_sel_heads(nsel, nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+    if ((e = launch(dev::k_un_plan, flat_grid(std::max(nsel, vcap), s), 256, s, X.ptr, X.list_unit, X.nlists, X.nunits, sel, ufirst, ucount,
+                    nsel, S.scanu.tot, S.totv, S.hdr, W.rec, vcap))
         != hipSuccess)
         return e;
-    const dev::UnArgs A{in, in_bytes, off, list_unit, start0, unit_last, sel, ufirst, ucount, nsel, out, out_values, vcap, out_ptr,
-                        S.hdr, W.rec, S.vbase, err};
-    // sized by the host's cap: waves past the real unit count exit
-    const uint32_t grid = static_cast<uint32_t>((vcap + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    const uint32_t tgrid = static_cast<uint32_t>((nsel + 4u * dev::kRunDefault - 1u) / (4u * dev::kRunDefault));
-    if (d1)
-        hipLaunchKernelGGL((dev::k_un_dec<true, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL((dev::k_un_dec<false, dev::kListsNC, dev::kListsMinW>), dim3(grid), dim3(256), 0, s, A);
-    if ((e = hipGetLastError()) != hipSuccess)
+    if ((e = launch_sel_heads(nsel, X.nunits, out_values, vcap, S.hdr, S.scanu, S.totv, S.prev, S.tilev, S.vbase, W.rec, out_ptr, err, s))
+        != hipSuccess)
         return e;
-    if (d1)
-        hipLaunchKernelGGL((dev::k_un_tails<true, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    else
-        hipLaunchKernelGGL((dev::k_un_tails<false, dev::kTailsNC>), dim3(tgrid), dim3(256), 0, s, A);
-    return hipGetLastError();
+    const dev::UnArgs A{.ix = X,
+                        .sel = sel,
+                        .ufirst = ufirst,
+                        .ucount = ucount,
+                        .nsel = nsel,
+                        .out = out,
+                        .out_values = out_values,
+                        .vcap = vcap,
+                        .out_ptr = out_ptr,
+                        .hdr = S.hdr,
+                        .rec = W.rec,
+                        .vbase = S.vbase,
+                        .err = err};
+    // sized by the host's cap: waves past the real unit count exit
+    if ((e = launch_by(d1, [](auto D1) { return dev::k_un_dec<D1, dev::kListsNC, dev::kListsMinW>; }, wave_grid(vcap, dev::kRunDefault), 256, s,
+                       A))
+        != hipSuccess)
+        return e;
+    return launch_by(d1, [](auto D1) { return dev::k_un_tails<D1, dev::kTailsNC>; }, wave_grid(nsel, dev::kRunDefault), 256, s, A);
 }
 
 } // namespace tpf
