@@ -151,7 +151,6 @@ def leg(tpf, L, ix, table, flat, qlist, pos, pptr, seed, args):
     copy_dst = torch.empty(in_bytes, dtype=torch.uint8, device=dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     src_p, dst_p = ctypes.c_void_p(ix.packed.data_ptr()), ctypes.c_void_p(copy_dst.data_ptr())
-    L.tpf_copy_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
 
     def copy():
         assert L.tpf_copy_async(dst_p, src_p, in_bytes, stream) == 0

@@ -15,14 +15,13 @@ import numpy as np
 import pytest
 
 import lists_difference_ref as dr
+from lists_index import Index
 import lists_ref as ref
 import lists_union_ref as ur
-from lists_index import Index
+import turbopfor_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "turbopfor-cpp_amd", "lib", "libturbopfor_amd.so")
-u64 = ctypes.c_uint64
-vp = ctypes.c_void_p
 EINVAL, ENODEV = -1, -3
 P = 0x1000  # a non-null pointer that is never followed: every call below is refused on the host
 STEPS = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 262144, 262145, 10 ** 6, 0x3FFFFFFF]
@@ -32,14 +31,8 @@ STEPS = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 26214
 def lib():
     if not os.path.exists(LIB):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "turbopfor-cpp_amd"), "-j8"])
-    L = ctypes.CDLL(LIB)
-    L.tpf_last_error.restype = ctypes.c_char_p
+    L = turbopfor_amd.declare(ctypes.CDLL(LIB))
     assert hasattr(L, "tpf_lists_difference"), "the library does not export tpf_lists_difference"
-    L.tpf_lists_difference_workspace_size.restype = ctypes.c_size_t
-    L.tpf_lists_difference_workspace_size.argtypes = [u64, u64]
-    L.tpf_lists_difference.restype = ctypes.c_int
-    L.tpf_lists_difference.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, vp,
-                                       ctypes.c_size_t, vp, vp]
     return L
 
 

@@ -15,6 +15,7 @@ import pytest
 
 import lists_enc_inputs as inp
 import lists_ref
+import turbopfor_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "turbopfor-cpp_amd", "lib", "libturbopfor_amd.so")
@@ -26,12 +27,7 @@ STEPS = [1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 4095, 4096, 4097, 10 ** 6, 0x7F
 def lib():
     if not os.path.exists(LIB):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "turbopfor-cpp_amd"), "-j8"])
-    L = ctypes.CDLL(LIB)
-    L.tpf_p4nenc256v32_lists_bound.restype = u64
-    L.tpf_p4nenc256v32_lists_bound.argtypes = [u64, u64]
-    L.tpf_p4nenc256v32_lists_workspace_size.restype = ctypes.c_size_t
-    L.tpf_p4nenc256v32_lists_workspace_size.argtypes = [u64, u64]
-    return L
+    return turbopfor_amd.declare(ctypes.CDLL(LIB))
 
 
 def test_symbols_exported(lib):
@@ -82,8 +78,6 @@ def test_bound_formula(lib):
 def test_no_cpu_fallback_without_device(lib):
     if subprocess.run([sys.executable, "-c", "import torch,sys;sys.exit(0 if torch.cuda.is_available() else 1)"]).returncode == 0:
         pytest.skip("a HIP device is visible")
-    lib.tpf_p4nenc256v32_lists.restype = ctypes.c_int
-    lib.tpf_last_error.restype = ctypes.c_char_p
     rc = lib.tpf_p4nenc256v32_lists(None, u64(0), None, u64(1), 0, None, None, u64(0), None, u64(1), None, ctypes.c_size_t(0), None,
                                     None)
     assert rc == -3  # TPF_ENODEV

@@ -10,10 +10,10 @@ import sys
 
 import pytest
 
+import turbopfor_amd
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "turbopfor-cpp_amd", "lib", "libturbopfor_amd.so")
-u64 = ctypes.c_uint64
-vp = ctypes.c_void_p
 EINVAL, ENODEV = -1, -3
 P = 0x1000  # a non-null pointer that is never followed: every call below is refused on the host
 STEPS = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 10 ** 6, 0x3FFFFFFF]
@@ -23,14 +23,7 @@ STEPS = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 10 **
 def lib():
     if not os.path.exists(LIB):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "turbopfor-cpp_amd"), "-j8"])
-    L = ctypes.CDLL(LIB)
-    L.tpf_last_error.restype = ctypes.c_char_p
-    L.tpf_lists_intersect_workspace_size.restype = ctypes.c_size_t
-    L.tpf_lists_intersect_workspace_size.argtypes = [u64, u64]
-    L.tpf_lists_intersect.restype = ctypes.c_int
-    L.tpf_lists_intersect.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, vp,
-                                      ctypes.c_size_t, vp, vp]
-    return L
+    return turbopfor_amd.declare(ctypes.CDLL(LIB))
 
 
 def _no_device():

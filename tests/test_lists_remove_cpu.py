@@ -16,6 +16,7 @@ import pytest
 
 import lists_ref as ref
 import lists_remove_ref as rr
+import turbopfor_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "turbopfor-cpp_amd", "lib", "libturbopfor_amd.so")
@@ -30,16 +31,7 @@ STEPS = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 10 **
 def lib():
     if not os.path.exists(LIB):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "turbopfor-cpp_amd"), "-j8"])
-    L = ctypes.CDLL(LIB)
-    L.tpf_last_error.restype = ctypes.c_char_p
-    L.tpf_lists_remove_bound.restype = u64
-    L.tpf_lists_remove_bound.argtypes = [u64, u64, u64]
-    L.tpf_lists_remove_workspace_size.restype = ctypes.c_size_t
-    L.tpf_lists_remove_workspace_size.argtypes = [u64] * 5
-    L.tpf_lists_remove.restype = ctypes.c_int
-    L.tpf_lists_remove.argtypes = [vp, u64, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, u64, vp, vp,
-                                   vp, vp, ctypes.c_size_t, vp, vp]
-    return L
+    return turbopfor_amd.declare(ctypes.CDLL(LIB))
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +49,10 @@ def test_symbols_exported(lib):
     assert {"tpf_lists_remove", "tpf_lists_remove_bound", "tpf_lists_remove_workspace_size"} <= exported
     with open(os.path.join(ROOT, "turbopfor-cpp_amd", "python", "turbopfor_amd.py")) as f:
         src = f.read()
-    assert "def lists_remove(" in src and "def lists_remove_bound(" in src and "L.tpf_lists_remove.argtypes" in src
+    assert "def lists_remove(" in src and "def lists_remove_bound(" in src
+    assert turbopfor_amd.prototypes()["tpf_lists_remove"] == (
+        ctypes.c_int, [vp, u64, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, u64, vp, vp, vp, vp,
+                       ctypes.c_size_t, vp, vp])
 
 
 def _call(lib, d_in=P, d_off=P, nunits=10, ptr=P, lu=P, nlists=5, d1=1, st=None, ul=P, pos=P, pos_values=100, pptr=P, ql=P, nq=3,

@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+import turbopfor_amd
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.environ.get("TPF_LIB") or os.path.join(ROOT, "turbopfor-cpp_amd", "lib", "libturbopfor_amd.so")
 FMT = {"32": 0, "128v32": 1, "256v32": 2, "64": 3, "128v64": 4, "256v64": 5}
@@ -63,14 +65,7 @@ LISTS = [[1280, 2048, 2048, 2048, 2048, 2304, 2816, 3328, 82944, 83456, 83968, 4
 def lib():
     if not os.path.exists(LIB):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "turbopfor-cpp_amd"), "-j8"])
-    L = ctypes.CDLL(LIB)
-    for name in list(ONE_COUNT) + ["tpf_enc_workspace_size", "tpf_p4ndec256v32_lists_workspace_size"]:
-        getattr(L, name).restype = ctypes.c_size_t
-    for name in ONE_COUNT:
-        getattr(L, name).argtypes = [ctypes.c_uint64]
-    L.tpf_enc_workspace_size.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint]
-    L.tpf_p4ndec256v32_lists_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
-    return L
+    return turbopfor_amd.declare(ctypes.CDLL(LIB))
 
 
 @pytest.mark.parametrize("name", sorted(ONE_COUNT))

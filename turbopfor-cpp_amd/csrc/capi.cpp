@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 
@@ -46,6 +47,37 @@ int prep_err(uint64_t * d_err, hipStream_t s)
         return TPF_OK;
     hipError_t e = tpf::fill_u32(d_err, 0xFFFFFFFFu, 2, s);
     return e == hipSuccess ? TPF_OK : hip_fail(e, "init d_err");
+}
+
+// The stream of an entry point that resets d_err itself, opened by that reset.
+int open_stream(void * stream, uint64_t * d_err, hipStream_t & s)
+{
+    s = static_cast<hipStream_t>(stream);
+    return prep_err(d_err, s);
+}
+
+// The same for an entry point that judges its arguments before it looks for the device.
+int open_device_stream(void * stream, uint64_t * d_err, hipStream_t & s)
+{
+    if (int rc = check_device())
+        return rc;
+    return open_stream(stream, d_err, s);
+}
+
+// d_err as the launchers take it.
+unsigned long long * dev_err(uint64_t * d_err) { return reinterpret_cast<unsigned long long *>(d_err); }
+
+// The epilogue of an entry point: its launcher's verdict as the return value.
+int done(hipError_t e, const char * name) { return e == hipSuccess ? TPF_OK : hip_fail(e, name); }
+
+// A count above the limit of the lists entry points, whose kernels index with
+// 32 bits.  The refusal's message, which names the counts, stays with the caller.
+bool over_limit(std::initializer_list<uint64_t> counts)
+{
+    for (uint64_t c : counts)
+        if (c > 0x7FFFFFFFull)
+            return true;
+    return false;
 }
 
 // The resident index of an entry point, its arguments in the public order: a
@@ -107,14 +139,11 @@ int tpf_p4dec256v32_batch(const uint8_t * d_in, uint64_t in_bytes, const uint64_
         return rc;
     if (nblocks && (!d_in || !d_off || !d_out))
         return fail(TPF_EINVAL, "tpf_p4dec256v32_batch: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_dec256v32(d_in, in_bytes, d_off, nblocks, d_out, nullptr,
-                                         reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4dec256v32_batch");
+    return done(tpf::launch_dec256v32(d_in, in_bytes, d_off, nblocks, d_out, nullptr, dev_err(d_err), s), "tpf_p4dec256v32_batch");
 }
-
 
 int tpf_p4d1dec256v32_batch(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nblocks, uint32_t * d_out,
                             const uint32_t * d_starts, uint64_t * d_err, void * stream)
@@ -123,12 +152,10 @@ int tpf_p4d1dec256v32_batch(const uint8_t * d_in, uint64_t in_bytes, const uint6
         return rc;
     if (nblocks && (!d_in || !d_off || !d_out || !d_starts))
         return fail(TPF_EINVAL, "tpf_p4d1dec256v32_batch: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_dec256v32(d_in, in_bytes, d_off, nblocks, d_out, d_starts,
-                                         reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4d1dec256v32_batch");
+    return done(tpf::launch_dec256v32(d_in, in_bytes, d_off, nblocks, d_out, d_starts, dev_err(d_err), s), "tpf_p4d1dec256v32_batch");
 }
 
 size_t tpf_p4d1dec256v32_chain_workspace_size(uint64_t nblocks) { return tpf::d1chain_workspace(nblocks); }
@@ -142,12 +169,11 @@ int tpf_p4d1dec256v32_chain_sums(const uint8_t * d_in, uint64_t in_bytes, const 
         return fail(TPF_EINVAL, "tpf_p4d1dec256v32_chain_sums: null pointer");
     if (ws_bytes < tpf_p4d1dec256v32_chain_workspace_size(nblocks))
         return fail(TPF_EINVAL, "tpf_p4d1dec256v32_chain_sums: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_d1chain_sums(d_in, in_bytes, d_off, nblocks, d_ws, ws_bytes, d_total,
-                                            reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4d1dec256v32_chain_sums");
+    return done(tpf::launch_d1chain_sums(d_in, in_bytes, d_off, nblocks, d_ws, ws_bytes, d_total, dev_err(d_err), s),
+                "tpf_p4d1dec256v32_chain_sums");
 }
 
 int tpf_p4d1dec256v32_chain_decode(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nblocks, uint32_t * d_out,
@@ -157,12 +183,11 @@ int tpf_p4d1dec256v32_chain_decode(const uint8_t * d_in, uint64_t in_bytes, cons
         return rc;
     if (nblocks && (!d_in || !d_off || !d_out || !d_ws))
         return fail(TPF_EINVAL, "tpf_p4d1dec256v32_chain_decode: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_d1chain_decode(d_in, in_bytes, d_off, nblocks, d_out, d_ws, base,
-                                              reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4d1dec256v32_chain_decode");
+    return done(tpf::launch_d1chain_decode(d_in, in_bytes, d_off, nblocks, d_out, d_ws, base, dev_err(d_err), s),
+                "tpf_p4d1dec256v32_chain_decode");
 }
 
 int tpf_p4d1dec256v32_chained(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nblocks, uint32_t * d_out,
@@ -194,12 +219,11 @@ int tpf_d1dec64_chain_sums(int fmt, const uint8_t * d_in, uint64_t in_bytes, con
         return fail(TPF_EINVAL, "tpf_d1dec64_chain_sums: null pointer");
     if (ws_bytes < tpf_d1dec64_chain_workspace_size(nunits))
         return fail(TPF_EINVAL, "tpf_d1dec64_chain_sums: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_d1chain64_sums(static_cast<uint32_t>(nb), d_in, in_bytes, d_off, nunits, d_ws, ws_bytes, d_total,
-                                              reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_d1dec64_chain_sums");
+    return done(tpf::launch_d1chain64_sums(static_cast<uint32_t>(nb), d_in, in_bytes, d_off, nunits, d_ws, ws_bytes, d_total,
+                                           dev_err(d_err), s), "tpf_d1dec64_chain_sums");
 }
 
 int tpf_d1dec64_chain_decode(int fmt, const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, uint64_t * d_out,
@@ -212,12 +236,11 @@ int tpf_d1dec64_chain_decode(int fmt, const uint8_t * d_in, uint64_t in_bytes, c
         return fail(TPF_EINVAL, "tpf_d1dec64_chain_decode: fmt must be TPF_FMT_128V64 or TPF_FMT_256V64");
     if (nunits && (!d_in || !d_off || !d_out || !d_ws))
         return fail(TPF_EINVAL, "tpf_d1dec64_chain_decode: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_d1chain64_decode(static_cast<uint32_t>(nb), d_in, in_bytes, d_off, nunits, d_out, d_ws, base,
-                                                reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_d1dec64_chain_decode");
+    return done(tpf::launch_d1chain64_decode(static_cast<uint32_t>(nb), d_in, in_bytes, d_off, nunits, d_out, d_ws, base, dev_err(d_err),
+                                             s), "tpf_d1dec64_chain_decode");
 }
 
 int tpf_d1dec64_chained(int fmt, const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, uint64_t * d_out,
@@ -259,9 +282,8 @@ static int enc256v32_common(const uint32_t * d_in, uint64_t nblocks, const uint3
     // must cover the worst case, or a block could be cut off unreported
     if (nblocks && out_cap < tpf_p4enc256v32_bound(nblocks))
         return fail(TPF_EINVAL, std::string(name) + ": out_cap below tpf_p4enc256v32_bound(nblocks)");
-    hipError_t e = tpf::launch_enc256v32(d_in, nblocks, d_starts, start0, d1, d_out, out_cap, d_off, d_ws, ws_bytes,
-                                         static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TPF_OK : hip_fail(e, name);
+    return done(tpf::launch_enc256v32(d_in, nblocks, d_starts, start0, d1, d_out, out_cap, d_off, d_ws, ws_bytes,
+                                      static_cast<hipStream_t>(stream)), name);
 }
 
 int tpf_p4enc256v32_batch(const uint32_t * d_in, uint64_t nblocks, uint8_t * d_out, uint64_t out_cap, uint64_t * d_off, void * d_ws,
@@ -269,7 +291,6 @@ int tpf_p4enc256v32_batch(const uint32_t * d_in, uint64_t nblocks, uint8_t * d_o
 {
     return enc256v32_common(d_in, nblocks, nullptr, 0, false, d_out, out_cap, d_off, d_ws, ws_bytes, stream, "tpf_p4enc256v32_batch");
 }
-
 
 int tpf_p4d1enc256v32_batch(const uint32_t * d_in, uint64_t nblocks, const uint32_t * d_starts, uint32_t start0, uint8_t * d_out,
                             uint64_t out_cap, uint64_t * d_off, void * d_ws, size_t ws_bytes, void * stream)
@@ -345,17 +366,17 @@ int tpf_dec_batch(int fmt, const uint8_t * d_in, uint64_t in_bytes, const uint64
         return fail(TPF_EINVAL, "tpf_dec_batch: unsupported (fmt, n)");
     if (nblocks && (!d_in || !d_off || !d_vals))
         return fail(TPF_EINVAL, "tpf_dec_batch: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
     hipError_t e;
     if (fmt == TPF_FMT_256V32 && n == 256)
         e = tpf::launch_dec256v32(d_in, in_bytes, d_off, nblocks, static_cast<uint32_t *>(d_vals),
-                                  static_cast<const uint32_t *>(d_starts), reinterpret_cast<unsigned long long *>(d_err), s);
+                                  static_cast<const uint32_t *>(d_starts), dev_err(d_err), s);
     else
         e = tpf::launch_dec_generic(fmt, d_in, in_bytes, d_off, nblocks, n, d_vals, d_starts,
-                                    reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_dec_batch");
+                                    dev_err(d_err), s);
+    return done(e, "tpf_dec_batch");
 }
 
 int tpf_enc_batch(int fmt, const void * d_vals, uint64_t nblocks, unsigned n, int d1, const void * d_starts, uint64_t start0,
@@ -381,7 +402,7 @@ int tpf_enc_batch(int fmt, const void * d_vals, uint64_t nblocks, unsigned n, in
                                   static_cast<const uint64_t *>(d_starts), start0, d_out, out_cap, d_off, d_ws, ws_bytes, s);
     else
         e = tpf::launch_enc_generic(fmt, d_vals, nblocks, n, d1 != 0, d_starts, start0, d_out, out_cap, d_off, d_ws, ws_bytes, s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_enc_batch");
+    return done(e, "tpf_enc_batch");
 }
 
 // ---- n-variant streams: floor(n/256) 256v32 blocks + one
@@ -432,8 +453,7 @@ int tpf_p4nenc256v32(const uint32_t * d_in, uint64_t n, int d1, uint32_t start0,
     if (int rc = tpf_enc_batch(TPF_FMT_32, d_in + nfull * 256, 1, tail, d1, starts, start0, img, ntail_image(n), tail_off, sub_ws,
                                sub_bytes, stream))
         return rc;
-    hipError_t e = tpf::launch_append(d_out, img, d_off + nfull, tail_off + 1, d_off + nfull + 1, s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4nenc256v32");
+    return done(tpf::launch_append(d_out, img, d_off + nfull, tail_off + 1, d_off + nfull + 1, s), "tpf_p4nenc256v32");
 }
 
 size_t tpf_p4ndec256v32_workspace_size(uint64_t n) { return kNHead + tpf_p4d1dec256v32_chain_workspace_size(n / 256); }
@@ -481,9 +501,7 @@ int tpf_p4ndec256v32(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
         return rc;
     if (!d_err)
         return TPF_OK;
-    hipError_t e = tpf::launch_err_merge(reinterpret_cast<unsigned long long *>(d_err), reinterpret_cast<unsigned long long *>(tail_err),
-                                         nfull, s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32");
+    return done(tpf::launch_err_merge(dev_err(d_err), reinterpret_cast<unsigned long long *>(tail_err), nfull, s), "tpf_p4ndec256v32");
 }
 
 // ---- many lists in one call: each list an n-variant stream, laid end to end
@@ -499,14 +517,13 @@ int tpf_p4ndec256v32_lists(const uint8_t * d_in, uint64_t in_bytes, const uint64
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: null pointer");
     if (nunits && nlists && ws_bytes < tpf_p4ndec256v32_lists_workspace_size(nunits, nlists))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: workspace too small");
-    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+    if (over_limit({nunits, nlists}))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists: nunits and nlists are limited to 0x7FFFFFFF");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, nullptr, nlists, d1, d_start0, nullptr);
-    hipError_t e = tpf::launch_lists_dec(X, d1 != 0, d_out, out_values, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists");
+    return done(tpf::launch_lists_dec(X, d1 != 0, d_out, out_values, d_ws, dev_err(d_err), s), "tpf_p4ndec256v32_lists");
 }
 
 // The per-unit bounds (1800 B per full block, tpf_enc_bound(TPF_FMT_32, 1, r)
@@ -537,16 +554,15 @@ int tpf_p4nenc256v32_lists(const uint32_t * d_in, uint64_t in_values, const uint
         return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: null pointer");
     if (nlists && nunits && (!d_in || !d_out))
         return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: null pointer");
-    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+    if (over_limit({nunits, nlists}))
         return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: nunits and nlists are limited to 0x7FFFFFFF");
     if (nlists && ws_bytes < tpf_p4nenc256v32_lists_workspace_size(nunits, nlists))
         return fail(TPF_EINVAL, "tpf_p4nenc256v32_lists: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_stream(stream, d_err, s))
         return rc;
-    hipError_t e = tpf::launch_lists_enc(d_in, in_values, d_list_ptr, nlists, d1 != 0, d1 ? d_start0 : nullptr, d_out, out_cap, d_off,
-                                         nunits, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4nenc256v32_lists");
+    return done(tpf::launch_lists_enc(d_in, in_values, d_list_ptr, nlists, d1 != 0, d1 ? d_start0 : nullptr, d_out, out_cap, d_off, nunits,
+                                      d_ws, dev_err(d_err), s), "tpf_p4nenc256v32_lists");
 }
 
 // ---- the read side of a resident index: the unit directory and the decode of
@@ -556,19 +572,16 @@ size_t tpf_lists_unit_base_workspace_size(uint64_t nlists) { return tpf::lists_u
 int tpf_lists_unit_base(const uint64_t * d_list_ptr, uint64_t nlists, uint32_t * d_list_unit, void * d_ws, size_t ws_bytes, uint64_t * d_err,
                         void * stream)
 {
-    if (nlists > 0x7FFFFFFFull)
+    if (over_limit({nlists}))
         return fail(TPF_EINVAL, "tpf_lists_unit_base: nlists is limited to 0x7FFFFFFF");
     if (!d_list_unit || (nlists && (!d_list_ptr || !d_ws)))
         return fail(TPF_EINVAL, "tpf_lists_unit_base: null pointer");
     if (nlists && ws_bytes < tpf_lists_unit_base_workspace_size(nlists))
         return fail(TPF_EINVAL, "tpf_lists_unit_base: workspace too small");
-    if (int rc = check_device())
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
-        return rc;
-    hipError_t e = tpf::launch_lists_unit_base(d_list_ptr, nlists, d_list_unit, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_unit_base");
+    return done(tpf::launch_lists_unit_base(d_list_ptr, nlists, d_list_unit, d_ws, dev_err(d_err), s), "tpf_lists_unit_base");
 }
 
 size_t tpf_p4ndec256v32_lists_select_workspace_size(uint64_t nsel, uint64_t out_values)
@@ -581,22 +594,18 @@ int tpf_p4ndec256v32_lists_select(const uint8_t * d_in, uint64_t in_bytes, const
                                   const uint32_t * d_start0, const uint32_t * d_sel, uint64_t nsel, uint32_t * d_out, uint64_t out_values,
                                   uint64_t * d_out_ptr, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nsel > 0x7FFFFFFFull
-        || (nsel && tpf::lists_select_unit_cap(nsel, out_values) > 0x7FFFFFFFull))
+    if (over_limit({nlists, nunits, nsel, nsel ? tpf::lists_select_unit_cap(nsel, out_values) : 0u}))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: nlists, nunits, nsel and out_values / 256 + nsel are limited to 0x7FFFFFFF");
     if (nsel && (!d_sel || !d_out_ptr || !d_in || !d_off || !d_list_ptr || !d_list_unit || !d_out || !d_ws))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: null pointer");
     if (nsel && ws_bytes < tpf_p4ndec256v32_lists_select_workspace_size(nsel, out_values))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_select: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, nullptr);
-    hipError_t e = tpf::launch_lists_select(X, d1 != 0, d_sel, nsel, d_out, out_values, d_out_ptr, d_ws,
-                                            reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_select");
+    return done(tpf::launch_lists_select(X, d1 != 0, d_sel, nsel, d_out, out_values, d_out_ptr, d_ws, dev_err(d_err), s),
+                "tpf_p4ndec256v32_lists_select");
 }
 
 // ---- block-range reads of a resident index: the skip table, the range search
@@ -608,38 +617,32 @@ int tpf_lists_unit_last(const uint8_t * d_in, uint64_t in_bytes, const uint64_t 
                         uint64_t nlists, const uint32_t * d_start0, uint32_t * d_unit_last, void * d_ws, size_t ws_bytes, uint64_t * d_err,
                         void * stream)
 {
-    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull)
+    if (over_limit({nunits, nlists}))
         return fail(TPF_EINVAL, "tpf_lists_unit_last: nunits and nlists are limited to 0x7FFFFFFF");
     if (nunits && nlists && (!d_in || !d_off || !d_list_ptr || !d_unit_last || !d_ws))
         return fail(TPF_EINVAL, "tpf_lists_unit_last: null pointer");
     if (nunits && nlists && ws_bytes < tpf_lists_unit_last_workspace_size(nunits, nlists))
         return fail(TPF_EINVAL, "tpf_lists_unit_last: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, nullptr, nlists, 1, d_start0, nullptr);
-    hipError_t e = tpf::launch_lists_unit_last(X, d_unit_last, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_unit_last");
+    return done(tpf::launch_lists_unit_last(X, d_unit_last, d_ws, dev_err(d_err), s), "tpf_lists_unit_last");
 }
 
 int tpf_lists_range_units(const uint32_t * d_list_unit, const uint32_t * d_unit_last, uint64_t nlists, uint64_t nunits,
                           const uint32_t * d_qlist, const uint32_t * d_qlo, const uint32_t * d_qhi, uint64_t nq, uint32_t * d_ufirst,
                           uint32_t * d_ucount, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull)
+    if (over_limit({nlists, nunits, nq}))
         return fail(TPF_EINVAL, "tpf_lists_range_units: nlists, nunits and nq are limited to 0x7FFFFFFF");
     if (nq && (!d_list_unit || !d_unit_last || !d_qlist || !d_qlo || !d_qhi || !d_ufirst || !d_ucount))
         return fail(TPF_EINVAL, "tpf_lists_range_units: null pointer");
-    if (int rc = check_device())
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
-        return rc;
-    hipError_t e = tpf::launch_lists_range_units(d_list_unit, d_unit_last, nlists, nunits, d_qlist, d_qlo, d_qhi, nq, d_ufirst, d_ucount,
-                                                 reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_range_units");
+    return done(tpf::launch_lists_range_units(d_list_unit, d_unit_last, nlists, nunits, d_qlist, d_qlo, d_qhi, nq, d_ufirst, d_ucount,
+                                              dev_err(d_err), s), "tpf_lists_range_units");
 }
 
 size_t tpf_p4ndec256v32_lists_units_workspace_size(uint64_t nsel, uint64_t out_values)
@@ -653,8 +656,7 @@ int tpf_p4ndec256v32_lists_units(const uint8_t * d_in, uint64_t in_bytes, const 
                                  const uint32_t * d_ufirst, const uint32_t * d_ucount, uint64_t nsel, uint32_t * d_out, uint64_t out_values,
                                  uint64_t * d_out_ptr, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nsel > 0x7FFFFFFFull
-        || (nsel && tpf::lists_select_unit_cap(nsel, out_values) > 0x7FFFFFFFull))
+    if (over_limit({nlists, nunits, nsel, nsel ? tpf::lists_select_unit_cap(nsel, out_values) : 0u}))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: nlists, nunits, nsel and out_values / 256 + nsel are limited to 0x7FFFFFFF");
     if (nsel && (!d_sel || !d_ufirst || !d_ucount || !d_out_ptr || !d_in || !d_off || !d_list_ptr || !d_list_unit || !d_out || !d_ws))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: null pointer");
@@ -662,20 +664,67 @@ int tpf_p4ndec256v32_lists_units(const uint8_t * d_in, uint64_t in_bytes, const 
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: null d_unit_last (delta-1 needs the skip table of tpf_lists_unit_last)");
     if (nsel && ws_bytes < tpf_p4ndec256v32_lists_units_workspace_size(nsel, out_values))
         return fail(TPF_EINVAL, "tpf_p4ndec256v32_lists_units: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_units(X, d1 != 0, d_sel, d_ufirst, d_ucount, nsel, d_out, out_values, d_out_ptr, d_ws,
-                                           reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_p4ndec256v32_lists_units");
+    return done(tpf::launch_lists_units(X, d1 != 0, d_sel, d_ufirst, d_ucount, nsel, d_out, out_values, d_out_ptr, d_ws, dev_err(d_err), s),
+                "tpf_p4ndec256v32_lists_units");
 }
 
-size_t tpf_lists_intersect_workspace_size(uint64_t nq, uint64_t probe_values)
+// ---- the probe calls on a resident index: intersection, union, difference.
+// The three take the same arguments and judge them in the same order: one body,
+// and per entry point its name, its launcher, its workspace size and the
+// refusal of a count above its limits.  Only the union is sized by out_values.
+size_t tpf_lists_intersect_workspace_size(uint64_t nq, uint64_t probe_values) { return tpf::lists_intersect_workspace(nq, probe_values); }
+
+size_t tpf_lists_union_workspace_size(uint64_t nq, uint64_t probe_values, uint64_t out_values)
 {
-    return tpf::lists_intersect_workspace(nq, probe_values);
+    return tpf::lists_union_workspace(nq, probe_values, out_values);
+}
+
+size_t tpf_lists_difference_workspace_size(uint64_t nq, uint64_t probe_values) { return tpf::lists_difference_workspace(nq, probe_values); }
+
+enum ProbeOp { kIntersect, kUnion, kDifference };
+
+static const struct
+{
+    const char * name;
+    decltype(&tpf::launch_lists_intersect) launch;
+    size_t (*ws_size)(uint64_t nq, uint64_t probe_values, uint64_t out_values);
+    const char * limits;
+} kProbeOps[] = {
+    {"tpf_lists_intersect", tpf::launch_lists_intersect,
+     [](uint64_t nq, uint64_t pv, uint64_t) { return tpf::lists_intersect_workspace(nq, pv); },
+     "tpf_lists_intersect: nlists, nunits, nq and probe_values are limited to 0x7FFFFFFF"},
+    {"tpf_lists_union", tpf::launch_lists_union, tpf::lists_union_workspace,
+     "tpf_lists_union: nlists, nunits, nq, probe_values and out_values / 256 + nq are limited to 0x7FFFFFFF"},
+    {"tpf_lists_difference", tpf::launch_lists_difference,
+     [](uint64_t nq, uint64_t pv, uint64_t) { return tpf::lists_difference_workspace(nq, pv); },
+     "tpf_lists_difference: nlists, nunits, nq and probe_values are limited to 0x7FFFFFFF"}};
+
+static int lists_probe(ProbeOp op, const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits,
+                       const uint64_t * d_list_ptr, const uint32_t * d_list_unit, uint64_t nlists, const uint32_t * d_start0,
+                       const uint32_t * d_unit_last, const uint32_t * d_probe, uint64_t probe_values, const uint64_t * d_probe_ptr,
+                       const uint32_t * d_qlist, uint64_t nq, uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr,
+                       uint32_t * d_out_pidx, uint32_t * d_out_tpos, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    const auto & O = kProbeOps[op];
+    if (over_limit({nlists, nunits, nq, probe_values, op == kUnion ? tpf::lists_select_unit_cap(nq, out_values) : 0u}))
+        return fail(TPF_EINVAL, O.limits);
+    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_unit_last || !d_probe_ptr || !d_qlist || !d_out_ptr || !d_ws))
+        return fail(TPF_EINVAL, std::string(O.name) + ": null pointer");
+    if ((probe_values && !d_probe) || (out_values && !d_out))
+        return fail(TPF_EINVAL, std::string(O.name) + ": null d_probe or d_out with a non-zero size");
+    if (nq && ws_bytes < O.ws_size(nq, probe_values, out_values))
+        return fail(TPF_EINVAL, std::string(O.name) + ": workspace too small");
+    if (int rc = check_device())
+        return rc;
+    // d_err is reset by the launcher, together with its workspace header
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
+    return done(O.launch(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx, d_out_tpos, d_ws,
+                         dev_err(d_err), static_cast<hipStream_t>(stream)),
+                O.name);
 }
 
 int tpf_lists_intersect(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
@@ -684,58 +733,20 @@ int tpf_lists_intersect(const uint8_t * d_in, uint64_t in_bytes, const uint64_t 
                         uint64_t nq, uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr, uint32_t * d_out_pidx,
                         uint32_t * d_out_tpos, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || probe_values > 0x7FFFFFFFull)
-        return fail(TPF_EINVAL, "tpf_lists_intersect: nlists, nunits, nq and probe_values are limited to 0x7FFFFFFF");
-    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_unit_last || !d_probe_ptr || !d_qlist || !d_out_ptr || !d_ws))
-        return fail(TPF_EINVAL, "tpf_lists_intersect: null pointer");
-    if ((probe_values && !d_probe) || (out_values && !d_out))
-        return fail(TPF_EINVAL, "tpf_lists_intersect: null d_probe or d_out with a non-zero size");
-    if (nq && ws_bytes < tpf_lists_intersect_workspace_size(nq, probe_values))
-        return fail(TPF_EINVAL, "tpf_lists_intersect: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // d_err is reset by the launcher, together with its workspace header
-    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_intersect(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
-                                               d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_intersect");
-}
-
-size_t tpf_lists_union_workspace_size(uint64_t nq, uint64_t probe_values, uint64_t out_values)
-{
-    return tpf::lists_union_workspace(nq, probe_values, out_values);
+    return lists_probe(kIntersect, d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last, d_probe,
+                       probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx, d_out_tpos, d_ws, ws_bytes, d_err,
+                       stream);
 }
 
 int tpf_lists_union(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
                     const uint32_t * d_list_unit, uint64_t nlists, const uint32_t * d_start0, const uint32_t * d_unit_last,
-                    const uint32_t * d_probe, uint64_t probe_values, const uint64_t * d_probe_ptr, const uint32_t * d_qlist, uint64_t nq,
-                    uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr, uint32_t * d_out_pidx, uint32_t * d_out_tpos,
-                    void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+                    const uint32_t * d_probe, uint64_t probe_values, const uint64_t * d_probe_ptr, const uint32_t * d_qlist,
+                    uint64_t nq, uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr, uint32_t * d_out_pidx,
+                    uint32_t * d_out_tpos, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || probe_values > 0x7FFFFFFFull
-        || tpf::lists_select_unit_cap(nq, out_values) > 0x7FFFFFFFull)
-        return fail(TPF_EINVAL,
-                    "tpf_lists_union: nlists, nunits, nq, probe_values and out_values / 256 + nq are limited to 0x7FFFFFFF");
-    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_unit_last || !d_probe_ptr || !d_qlist || !d_out_ptr || !d_ws))
-        return fail(TPF_EINVAL, "tpf_lists_union: null pointer");
-    if ((probe_values && !d_probe) || (out_values && !d_out))
-        return fail(TPF_EINVAL, "tpf_lists_union: null d_probe or d_out with a non-zero size");
-    if (nq && ws_bytes < tpf_lists_union_workspace_size(nq, probe_values, out_values))
-        return fail(TPF_EINVAL, "tpf_lists_union: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // d_err is reset by the launcher, together with its workspace header
-    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_union(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
-                                           d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_union");
-}
-
-size_t tpf_lists_difference_workspace_size(uint64_t nq, uint64_t probe_values)
-{
-    return tpf::lists_difference_workspace(nq, probe_values);
+    return lists_probe(kUnion, d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last, d_probe,
+                       probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx, d_out_tpos, d_ws, ws_bytes, d_err,
+                       stream);
 }
 
 int tpf_lists_difference(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
@@ -744,35 +755,19 @@ int tpf_lists_difference(const uint8_t * d_in, uint64_t in_bytes, const uint64_t
                          uint64_t nq, uint32_t * d_out, uint64_t out_values, uint64_t * d_out_ptr, uint32_t * d_out_pidx,
                          uint32_t * d_out_tpos, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || probe_values > 0x7FFFFFFFull)
-        return fail(TPF_EINVAL, "tpf_lists_difference: nlists, nunits, nq and probe_values are limited to 0x7FFFFFFF");
-    if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_unit_last || !d_probe_ptr || !d_qlist || !d_out_ptr || !d_ws))
-        return fail(TPF_EINVAL, "tpf_lists_difference: null pointer");
-    if ((probe_values && !d_probe) || (out_values && !d_out))
-        return fail(TPF_EINVAL, "tpf_lists_difference: null d_probe or d_out with a non-zero size");
-    if (nq && ws_bytes < tpf_lists_difference_workspace_size(nq, probe_values))
-        return fail(TPF_EINVAL, "tpf_lists_difference: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // d_err is reset by the launcher, together with its workspace header
-    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, 1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_difference(X, d_probe, probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx,
-                                                d_out_tpos, d_ws, reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_difference");
+    return lists_probe(kDifference, d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d_start0, d_unit_last, d_probe,
+                       probe_values, d_probe_ptr, d_qlist, nq, d_out, out_values, d_out_ptr, d_out_pidx, d_out_tpos, d_ws, ws_bytes, d_err,
+                       stream);
 }
 
-size_t tpf_lists_gather_workspace_size(uint64_t nq, uint64_t pos_values)
-{
-    return tpf::lists_gather_workspace(nq, pos_values);
-}
+size_t tpf_lists_gather_workspace_size(uint64_t nq, uint64_t pos_values) { return tpf::lists_gather_workspace(nq, pos_values); }
 
 int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
                      const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last,
                      const uint32_t * d_pos, uint64_t pos_values, const uint64_t * d_pos_ptr, const uint32_t * d_qlist, uint64_t nq,
                      uint32_t * d_out, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
 {
-    if (nlists > 0x7FFFFFFFull || nunits > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || pos_values > 0x7FFFFFFFull)
+    if (over_limit({nlists, nunits, nq, pos_values}))
         return fail(TPF_EINVAL, "tpf_lists_gather: nlists, nunits, nq and pos_values are limited to 0x7FFFFFFF");
     if (nq && (!d_in || !d_off || !d_list_ptr || !d_list_unit || !d_pos_ptr || !d_qlist || !d_ws))
         return fail(TPF_EINVAL, "tpf_lists_gather: null pointer");
@@ -787,12 +782,19 @@ int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     hipStream_t s = static_cast<hipStream_t>(stream);
     // d_err is reset by the launcher, together with its workspace header
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_gather(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nq, d_out, d_ws,
-                                            reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_gather");
+    return done(tpf::launch_lists_gather(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nq, d_out, d_ws, dev_err(d_err), s),
+                "tpf_lists_gather");
 }
 
 // ---- postings appended to a resident index (p4_lists_append.hip)
+// A null pointer of the output side, which tpf_lists_append and tpf_lists_remove share, for a result of n lists: the
+// three directories written always; the workspace, and d_out when it has a capacity, once there are lists.
+static bool index_out_null(uint64_t n, const uint8_t * d_out, uint64_t out_cap, const uint64_t * d_off_out, const uint64_t * d_list_ptr_out,
+                           const uint32_t * d_list_unit_out, const void * d_ws)
+{
+    return !d_off_out || !d_list_ptr_out || !d_list_unit_out || (n && (!d_ws || (out_cap && !d_out)));
+}
+
 uint64_t tpf_lists_append_units_bound(uint64_t nunits, uint64_t nlists_out, uint64_t add_values)
 {
     return nunits + add_values / 256u + std::min(nlists_out, add_values);
@@ -817,11 +819,9 @@ int tpf_lists_append(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
 {
     if (nlists_out < nlists)
         return fail(TPF_EINVAL, "tpf_lists_append: nlists_out is below nlists (lists are never removed)");
-    if (nunits > 0x7FFFFFFFull || nlists_out > 0x7FFFFFFFull || units_cap > 0x7FFFFFFFull || add_values > 0x7FFFFFFFull)
+    if (over_limit({nunits, nlists_out, units_cap, add_values}))
         return fail(TPF_EINVAL, "tpf_lists_append: nunits, nlists_out, units_cap and add_values are limited to 0x7FFFFFFF");
-    if (!d_off_out || !d_list_ptr_out || !d_list_unit_out)
-        return fail(TPF_EINVAL, "tpf_lists_append: null pointer");
-    if (nlists_out && (!d_add_ptr || !d_ws || (out_cap && !d_out)))
+    if (index_out_null(nlists_out, d_out, out_cap, d_off_out, d_list_ptr_out, d_list_unit_out, d_ws) || (nlists_out && !d_add_ptr))
         return fail(TPF_EINVAL, "tpf_lists_append: null pointer");
     if (nlists && nunits && (!d_in || !d_off || !d_list_ptr || !d_list_unit))
         return fail(TPF_EINVAL, "tpf_lists_append: null pointer (the old index)");
@@ -832,16 +832,13 @@ int tpf_lists_append(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
         return fail(TPF_EINVAL, "tpf_lists_append: null d_add with a non-zero add_values");
     if (nlists_out && ws_bytes < tpf_lists_append_workspace_size(nunits, nlists_out, add_values))
         return fail(TPF_EINVAL, "tpf_lists_append: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_append(X, d1 != 0, d_add, add_values, d_add_ptr, nlists_out, d_out, out_cap, d_off_out, units_cap,
-                                            d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
-                                            reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_append");
+    return done(tpf::launch_lists_append(X, d1 != 0, d_add, add_values, d_add_ptr, nlists_out, d_out, out_cap, d_off_out, units_cap,
+                                         d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws, dev_err(d_err), s),
+                "tpf_lists_append");
 }
 
 // ---- postings deleted from a resident index (p4_lists_remove.hip)
@@ -863,14 +860,12 @@ int tpf_lists_remove(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
                      uint64_t * d_list_ptr_out, uint32_t * d_list_unit_out, uint32_t * d_unit_last_out, void * d_ws, size_t ws_bytes,
                      uint64_t * d_err, void * stream)
 {
-    if (nunits > 0x7FFFFFFFull || nlists > 0x7FFFFFFFull || nq > 0x7FFFFFFFull || pos_values > 0x7FFFFFFFull
-        || stage_values > 0x7FFFFFFFull || units_cap > 0x7FFFFFFFull || stage_values / 256u + nq + 1u > 0x7FFFFFFFull)
+    if (over_limit({nunits, nlists, nq, pos_values, stage_values, units_cap, stage_values / 256u + nq + 1u}))
         return fail(TPF_EINVAL,
                     "tpf_lists_remove: nunits, nlists, nq, pos_values, stage_values, units_cap and stage_values / 256 + nq + 1 are "
                     "limited to 0x7FFFFFFF");
-    if (!d_off_out || !d_list_ptr_out || !d_list_unit_out)
-        return fail(TPF_EINVAL, "tpf_lists_remove: null pointer");
-    if (nlists && (!d_list_ptr || !d_list_unit || !d_ws || (out_cap && !d_out)))
+    if (index_out_null(nlists, d_out, out_cap, d_off_out, d_list_ptr_out, d_list_unit_out, d_ws)
+        || (nlists && (!d_list_ptr || !d_list_unit)))
         return fail(TPF_EINVAL, "tpf_lists_remove: null pointer");
     if (nlists && nunits && (!d_in || !d_off))
         return fail(TPF_EINVAL, "tpf_lists_remove: null pointer (the old index)");
@@ -883,16 +878,13 @@ int tpf_lists_remove(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
         return fail(TPF_EINVAL, "tpf_lists_remove: null d_pos with a non-zero pos_values");
     if (nlists && ws_bytes < tpf_lists_remove_workspace_size(nunits, nlists, nq, pos_values, stage_values))
         return fail(TPF_EINVAL, "tpf_lists_remove: workspace too small");
-    if (int rc = check_device())
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = prep_err(d_err, s))
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
         return rc;
     const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
-    hipError_t e = tpf::launch_lists_remove(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nlists ? nq : 0u, stage_values, d_out, out_cap,
-                                            d_off_out, units_cap, d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
-                                            reinterpret_cast<unsigned long long *>(d_err), s);
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_lists_remove");
+    return done(tpf::launch_lists_remove(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nlists ? nq : 0u, stage_values, d_out, out_cap,
+                                         d_off_out, units_cap, d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
+                                         dev_err(d_err), s), "tpf_lists_remove");
 }
 
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
@@ -901,8 +893,7 @@ int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)
         return rc;
     if (bytes && (!dst || !src))
         return fail(TPF_EINVAL, "tpf_copy_async: null pointer");
-    hipError_t e = tpf::launch_copy(dst, src, bytes, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TPF_OK : hip_fail(e, "tpf_copy_async");
+    return done(tpf::launch_copy(dst, src, bytes, static_cast<hipStream_t>(stream)), "tpf_copy_async");
 }
 
 } // extern "C"

@@ -9,6 +9,7 @@ offsets (the reference's callers chain blocks through the returned pointer).
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +66,72 @@ def kernel_md5():
     return _md5(files, root)
 
 
+# ---- the C ABI, read from the headers that state it -------------------------
+HEADERS = tuple(os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("turbopfor_gpu.h", "turbopfor_capi.h"))
+_C_TYPES = {"uint64_t": c_u64, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t,
+            "int": ctypes.c_int, "unsigned": ctypes.c_uint}
+_C_WORDS = set(_C_TYPES) | {"void", "char", "short", "long", "signed", "float", "double"}
+
+
+def _c_type(decl, where, ret=False):
+    """The ctypes type of one parameter (with or without its name) or of a
+    return type: the table of prototypes(), nothing beyond it."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return ctypes.c_char_p if ret and words == ["const", "char", "*"] else c_vp
+    words = [w for w in words if w != "const"]
+    if not ret and len(words) == 2 and re.fullmatch(r"[A-Za-z_]\w*", words[1]) and words[1] not in _C_WORDS:
+        words.pop()  # the parameter's name
+    if len(words) == 1 and (words[0] in _C_TYPES or (ret and words[0] == "void")):
+        return _C_TYPES.get(words[0])
+    raise TpfError(f"{where}: no ctypes type for '{' '.join(decl.split())}'")
+
+
+def prototypes(headers=HEADERS):
+    """{name: (restype, [argtypes])} of every tpf_* function the public
+    headers declare (tpfm_* of the measurement library's header), read from the
+    headers themselves (comments and preprocessor lines stripped), so that
+    nothing restates the ABI by hand.  Pointer parameters are c_void_p;
+    uint64_t, int64_t, uint32_t, size_t, int and unsigned their ctypes
+    namesakes; a void return is None, a const char * return c_char_p, any
+    other pointer return c_void_p.  Strict: a type outside that table, a tpf_
+    declaration this parse cannot read or a missing header raises TpfError
+    naming the file and the declaration."""
+    protos = {}
+    for path in headers:
+        try:
+            with open(path) as f:
+                text = f.read()
+        except OSError as e:
+            raise TpfError(f"{path}: header not found ({e})")
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+        text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+        text = re.sub(r'extern\s+"C"\s*\{', "", text)
+        for stmt in text.split(";"):
+            if not re.search(r"\btpfm?_\w+\s*\(", stmt):
+                continue
+            where = f"{path}: '{' '.join(stmt.split())}'"
+            m = re.fullmatch(r"\s*([\w\s*]+?)\b(tpfm?_\w+)\s*\(([^()]*)\)\s*", stmt)
+            if not m:
+                raise TpfError(f"{where}: not a prototype this parse reads")
+            ret, name, params = m.groups()
+            params = [] if params.strip() == "void" else params.split(",")
+            protos[name] = (_c_type(ret, where, ret=True), [_c_type(p, where) for p in params])
+    return protos
+
+
+def declare(L, protos=None):
+    """Give every function of protos (default: prototypes()) that the loaded
+    ctypes.CDLL L exports its restype and argtypes; returns L.  Symbols L lacks
+    are skipped (an older build loaded through TPF_LIB for an A/B run).  No
+    torch."""
+    for name, (restype, argtypes) in (protos or prototypes()).items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+    return L
+
+
 def lib():
     """Load (building if needed) the in-tree HIP library."""
     global _lib
@@ -76,144 +143,7 @@ def lib():
 
         if not os.path.exists(LIB_PATH):
             build()
-        L = ctypes.CDLL(LIB_PATH)
-        L.tpf_last_error.restype = ctypes.c_char_p
-        L.tpf_device_count.restype = ctypes.c_int
-        L.tpf_p4dec256v32_batch.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]
-        L.tpf_p4d1dec256v32_batch.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp]
-        L.tpf_p4enc256v32_bound.argtypes = [c_u64]
-        L.tpf_p4enc256v32_bound.restype = c_u64
-        L.tpf_p4enc256v32_workspace_size.argtypes = [c_u64]
-        L.tpf_p4enc256v32_workspace_size.restype = ctypes.c_size_t
-        L.tpf_p4enc256v32_batch.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.tpf_p4d1enc256v32_batch.argtypes = [c_vp, c_u64, c_vp, ctypes.c_uint32, c_vp, c_u64, c_vp, c_vp,
-                                              ctypes.c_size_t, c_vp]
-        L.tpf_enc_bound.argtypes = [ctypes.c_int, c_u64, ctypes.c_uint]
-        L.tpf_enc_bound.restype = c_u64
-        L.tpf_enc_workspace_size.argtypes = [ctypes.c_int, c_u64, ctypes.c_uint]
-        L.tpf_enc_workspace_size.restype = ctypes.c_size_t
-        L.tpf_dec_batch.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, ctypes.c_uint, c_vp, c_vp, c_vp, c_vp]
-        L.tpf_enc_batch.argtypes = [ctypes.c_int, c_vp, c_u64, ctypes.c_uint, ctypes.c_int, c_vp, c_u64, c_vp, c_u64,
-                                    c_vp, c_vp, ctypes.c_size_t, c_vp]
-        L.tpf_p4d1dec256v32_chain_workspace_size.argtypes = [c_u64]
-        L.tpf_p4d1dec256v32_chain_workspace_size.restype = ctypes.c_size_t
-        L.tpf_p4d1dec256v32_chained.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_uint32, c_vp, ctypes.c_size_t,
-                                                c_vp, c_vp]
-        L.tpf_p4d1dec256v32_chain_sums.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]
-        L.tpf_p4d1dec256v32_chain_decode.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]
-        L.tpf_p4nenc256v32_bound.argtypes = [c_u64]
-        L.tpf_p4nenc256v32_bound.restype = c_u64
-        L.tpf_p4nenc256v32_workspace_size.argtypes = [c_u64]
-        L.tpf_p4nenc256v32_workspace_size.restype = ctypes.c_size_t
-        L.tpf_p4nenc256v32.argtypes = [c_vp, c_u64, ctypes.c_int, ctypes.c_uint32, c_vp, c_u64, c_vp, c_vp,
-                                       ctypes.c_size_t, c_vp]
-        L.tpf_p4ndec256v32_workspace_size.argtypes = [c_u64]
-        L.tpf_p4ndec256v32_workspace_size.restype = ctypes.c_size_t
-        L.tpf_p4ndec256v32.argtypes = [c_vp, c_u64, c_vp, c_u64, ctypes.c_int, ctypes.c_uint32, c_vp, c_vp,
-                                       ctypes.c_size_t, c_vp, c_vp]
-        # round-4 entry points: absent from older builds loaded through TPF_LIB for A/B runs
-        if hasattr(L, "tpf_d1dec64_chained"):
-            L.tpf_d1dec64_chain_workspace_size.argtypes = [c_u64]
-            L.tpf_d1dec64_chain_workspace_size.restype = ctypes.c_size_t
-            L.tpf_d1dec64_chained.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_d1dec64_chain_sums.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]
-            L.tpf_d1dec64_chain_decode.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp]
-            for name in ("tpf_p4d1dec256v64_chained", "tpf_p4d1dec128v64_chained"):
-                getattr(L, name).argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_vp]
-                getattr(L, name).restype = ctypes.c_int
-            for name in ("tpf_d1dec64_chained", "tpf_d1dec64_chain_sums", "tpf_d1dec64_chain_decode"):
-                getattr(L, name).restype = ctypes.c_int
-        # the many-lists decode: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_p4ndec256v32_lists"):
-            L.tpf_p4ndec256v32_lists_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_p4ndec256v32_lists_workspace_size.restype = ctypes.c_size_t
-            L.tpf_p4ndec256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp,
-                                                 ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_p4ndec256v32_lists.restype = ctypes.c_int
-        # the many-lists encode: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_p4nenc256v32_lists"):
-            L.tpf_p4nenc256v32_lists_bound.argtypes = [c_u64, c_u64]
-            L.tpf_p4nenc256v32_lists_bound.restype = c_u64
-            L.tpf_p4nenc256v32_lists_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_p4nenc256v32_lists_workspace_size.restype = ctypes.c_size_t
-            L.tpf_p4nenc256v32_lists.argtypes = [c_vp, c_u64, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp, c_u64, c_vp,
-                                                 ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_p4nenc256v32_lists.restype = ctypes.c_int
-        # the unit directory and the selective decode: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_p4ndec256v32_lists_select"):
-            L.tpf_lists_unit_base_workspace_size.argtypes = [c_u64]
-            L.tpf_lists_unit_base_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_unit_base.argtypes = [c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_unit_base.restype = ctypes.c_int
-            L.tpf_p4ndec256v32_lists_select_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_p4ndec256v32_lists_select_workspace_size.restype = ctypes.c_size_t
-            L.tpf_p4ndec256v32_lists_select.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64,
-                                                        c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_p4ndec256v32_lists_select.restype = ctypes.c_int
-        # the skip table, the range search and the units decode: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_p4ndec256v32_lists_units"):
-            L.tpf_lists_unit_last_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_lists_unit_last_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_unit_last.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_unit_last.restype = ctypes.c_int
-            L.tpf_lists_range_units.argtypes = [c_vp, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp]
-            L.tpf_lists_range_units.restype = ctypes.c_int
-            L.tpf_p4ndec256v32_lists_units_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_p4ndec256v32_lists_units_workspace_size.restype = ctypes.c_size_t
-            L.tpf_p4ndec256v32_lists_units.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
-                                                       c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_p4ndec256v32_lists_units.restype = ctypes.c_int
-        # the intersection with a resident index: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_lists_intersect"):
-            L.tpf_lists_intersect_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_lists_intersect_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_intersect.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
-                                              c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_intersect.restype = ctypes.c_int
-        # the union with a resident index: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_lists_union"):
-            L.tpf_lists_union_workspace_size.argtypes = [c_u64, c_u64, c_u64]
-            L.tpf_lists_union_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_union.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
-                                          c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_union.restype = ctypes.c_int
-        # the difference with a resident index: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_lists_difference"):
-            L.tpf_lists_difference_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_lists_difference_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_difference.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_u64,
-                                               c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_difference.restype = ctypes.c_int
-        # values at list positions of a resident index: absent from older builds loaded through TPF_LIB
-        if hasattr(L, "tpf_lists_gather"):
-            L.tpf_lists_gather_workspace_size.argtypes = [c_u64, c_u64]
-            L.tpf_lists_gather_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_gather.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp,
-                                           c_u64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_gather.restype = ctypes.c_int
-        if hasattr(L, "tpf_lists_append"):
-            L.tpf_lists_append_units_bound.argtypes = [c_u64, c_u64, c_u64]
-            L.tpf_lists_append_units_bound.restype = c_u64
-            L.tpf_lists_append_bound.argtypes = [c_u64, c_u64, c_u64]
-            L.tpf_lists_append_bound.restype = c_u64
-            L.tpf_lists_append_workspace_size.argtypes = [c_u64, c_u64, c_u64]
-            L.tpf_lists_append_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_append.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_u64,
-                                           c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_append.restype = ctypes.c_int
-        if hasattr(L, "tpf_lists_remove"):
-            L.tpf_lists_remove_bound.argtypes = [c_u64, c_u64, c_u64]
-            L.tpf_lists_remove_bound.restype = c_u64
-            L.tpf_lists_remove_workspace_size.argtypes = [c_u64, c_u64, c_u64, c_u64, c_u64]
-            L.tpf_lists_remove_workspace_size.restype = ctypes.c_size_t
-            L.tpf_lists_remove.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp, c_u64, c_vp, c_vp,
-                                           c_u64, c_u64, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]
-            L.tpf_lists_remove.restype = ctypes.c_int
-        for name in ("tpf_p4nenc256v32", "tpf_p4ndec256v32", "tpf_p4dec256v32_batch", "tpf_p4d1dec256v32_batch", "tpf_p4enc256v32_batch",
-                     "tpf_p4d1enc256v32_batch", "tpf_dec_batch", "tpf_enc_batch", "tpf_p4d1dec256v32_chained",
-                     "tpf_p4d1dec256v32_chain_sums", "tpf_p4d1dec256v32_chain_decode"):
-            getattr(L, name).restype = ctypes.c_int
-        _lib = L
+        _lib = declare(ctypes.CDLL(LIB_PATH))
     return _lib
 
 
@@ -228,6 +158,25 @@ def _stream(torch):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _index(packed, offsets, list_ptr, list_unit):
+    """The arguments every call on a resident lists index begins with: packed,
+    its length, offsets, nunits, list_ptr, list_unit, nlists."""
+    return (_ptr(packed), packed.numel(), _ptr(offsets), offsets.numel() - 1, _ptr(list_ptr), _ptr(list_unit),
+            list_ptr.numel() - 1)
+
+
+def _ws(ws, device, size_export, *counts):
+    """The workspace of a call: the caller's ws when it holds the bytes
+    size_export(*counts) asks for, else a fresh uint8 tensor of that size (of
+    1 byte for a size of 0) on device."""
+    size = int(size_export(*counts))
+    if ws is None or ws.numel() < size:
+        import torch
+
+        ws = torch.empty(max(size, 1), dtype=torch.uint8, device=device)
+    return ws
 
 
 def dec256v32(packed, offsets, nblocks, out=None, starts=None, err=None):
@@ -264,21 +213,7 @@ def measure():
         lib()
         if not os.path.exists(MEASURE_PATH):
             build()
-        M = ctypes.CDLL(MEASURE_PATH)
-        M.tpfm_probe256v32.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp]
-        M.tpfm_dec256v32_path.argtypes = [ctypes.c_int, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp]
-        M.tpfm_probe256v64.argtypes = [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp]
-        M.tpfm_probe_hbm.argtypes = [ctypes.c_int, c_vp, c_vp, c_u64, c_vp]
-        M.tpfm_enc256v32.argtypes = [ctypes.c_int, c_vp, c_u64, ctypes.c_int, c_vp, ctypes.c_uint32, c_vp, c_u64, c_vp, c_vp,
-                                     ctypes.c_size_t, c_vp]
-        M.tpfm_enc256v32_workspace_size.argtypes = [ctypes.c_int, c_u64]
-        M.tpfm_enc256v32_workspace_size.restype = ctypes.c_size_t
-        M.tpfm_run_scan_workspace_size.argtypes = [c_u64]
-        M.tpfm_run_scan_workspace_size.restype = ctypes.c_size_t
-        M.tpfm_run_scan.argtypes = [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-        for name in ("tpfm_probe256v32", "tpfm_probe256v64", "tpfm_probe_hbm", "tpfm_enc256v32", "tpfm_run_scan"):
-            getattr(M, name).restype = ctypes.c_int
-        _mlib = M
+        _mlib = declare(ctypes.CDLL(MEASURE_PATH), prototypes([os.path.join(PKG_DIR, "measure", "tpf_measure.h")]))
     return _mlib
 
 
@@ -364,9 +299,7 @@ def enc256v32(values, d1=False, starts=None, start0=0, out=None, offs=None, ws=N
         out = torch.empty(int(L.tpf_p4enc256v32_bound(nb)), dtype=torch.uint8, device=values.device)
     if offs is None:
         offs = torch.empty(nb + 1, dtype=torch.int64, device=values.device)
-    ws_bytes = int(L.tpf_p4enc256v32_workspace_size(nb))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=values.device)
+    ws = _ws(ws, values.device, L.tpf_p4enc256v32_workspace_size, nb)
     if d1:
         rc = L.tpf_p4d1enc256v32_batch(_ptr(values), nb, _ptr(starts), ctypes.c_uint32(start0 & 0xFFFFFFFF),
                                        _ptr(out), out.numel(), _ptr(offs), _ptr(ws), ws.numel(), _stream(torch))
@@ -407,12 +340,9 @@ def enc_batch(fmt, values, nblocks, n, d1=False, starts=None, start0=0, out=None
     cap = out.numel()
     if offs is None:
         offs = torch.empty(nblocks + 1, dtype=torch.int64, device=values.device)
-    wsb = int(L.tpf_enc_workspace_size(f, nblocks, n))
-    if ws is None or ws.numel() < wsb:
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=values.device)
-    wsb = ws.numel()
+    ws = _ws(ws, values.device, L.tpf_enc_workspace_size, f, nblocks, n)
     rc = L.tpf_enc_batch(f, _ptr(values), nblocks, n, 1 if d1 else 0, _ptr(starts),
-                         ctypes.c_uint64(start0 & ((1 << 64) - 1)), _ptr(out), cap, _ptr(offs), _ptr(ws), wsb,
+                         ctypes.c_uint64(start0 & ((1 << 64) - 1)), _ptr(out), cap, _ptr(offs), _ptr(ws), ws.numel(),
                          _stream(torch))
     _check(rc)
     return out[: int(offs[-1].item())], offs
@@ -446,9 +376,7 @@ class D1Chain:
 
         self.packed, self.offsets, self.nblocks = packed, offsets, nblocks
         L = lib()
-        ws_bytes = int(L.tpf_p4d1dec256v32_chain_workspace_size(nblocks))
-        if ws is None or ws.numel() < ws_bytes:
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+        ws = _ws(ws, packed.device, L.tpf_p4d1dec256v32_chain_workspace_size, nblocks)
         self.ws, self.ws_bytes = ws, ws.numel()
         self.total = torch.zeros(1, dtype=torch.int32, device=packed.device) if total is None else total
 
@@ -486,9 +414,7 @@ class D1Chain64:
 
         self.fmt, self.width = FMT[fmt], _UNIT[fmt]
         self.packed, self.offsets, self.nunits = packed, offsets, nunits
-        ws_bytes = int(lib().tpf_d1dec64_chain_workspace_size(nunits))
-        if ws is None or ws.numel() < ws_bytes:
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+        ws = _ws(ws, packed.device, lib().tpf_d1dec64_chain_workspace_size, nunits)
         self.ws, self.ws_bytes = ws, ws.numel()
         self.total = torch.zeros(1, dtype=torch.int64, device=packed.device) if total is None else total
 
@@ -519,9 +445,7 @@ def dec256v32_chained(packed, offsets, nblocks, start0=0, out=None, err=None, ws
     if out is None:
         out = torch.empty((nblocks, 256), dtype=torch.int32, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4d1dec256v32_chain_workspace_size(nblocks))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    ws = _ws(ws, packed.device, L.tpf_p4d1dec256v32_chain_workspace_size, nblocks)
     rc = L.tpf_p4d1dec256v32_chained(_ptr(packed), packed.numel(), _ptr(offsets), nblocks, _ptr(out),
                                      ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(ws), ws.numel(), _ptr(err),
                                      _stream(torch))
@@ -541,9 +465,7 @@ def dec64_chained(fmt, packed, offsets, nunits, start0=0, out=None, err=None, ws
     if out is None:
         out = torch.empty((nunits, width), dtype=torch.int64, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_d1dec64_chain_workspace_size(nunits))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    ws = _ws(ws, packed.device, L.tpf_d1dec64_chain_workspace_size, nunits)
     args = (_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(out), ctypes.c_uint64(start0 & 0xFFFFFFFFFFFFFFFF), _ptr(ws),
             ws.numel(), _ptr(err), _stream(torch))
     rc = getattr(L, f"tpf_p4d1dec{fmt}_chained")(*args) if named else L.tpf_d1dec64_chained(FMT[fmt], *args)
@@ -576,9 +498,7 @@ def encn256v32(values, d1=False, start0=0, out=None, offs=None, ws=None):
         out = torch.empty(int(L.tpf_p4nenc256v32_bound(n)), dtype=torch.uint8, device=values.device)
     if offs is None:
         offs = torch.empty(n_units(n) + 1, dtype=torch.int64, device=values.device)
-    ws_bytes = int(L.tpf_p4nenc256v32_workspace_size(n))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=values.device)
+    ws = _ws(ws, values.device, L.tpf_p4nenc256v32_workspace_size, n)
     _check(L.tpf_p4nenc256v32(_ptr(values), n, int(bool(d1)), ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), out.numel(),
                               _ptr(offs), _ptr(ws), ws.numel(), _stream(torch)))
     if not trim:
@@ -595,9 +515,7 @@ def decn256v32(packed, offsets, n, d1=False, start0=0, out=None, err=None, ws=No
     if out is None:
         out = torch.empty(n, dtype=torch.int32, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4ndec256v32_workspace_size(n))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=packed.device)
+    ws = _ws(ws, packed.device, L.tpf_p4ndec256v32_workspace_size, n)
     _check(L.tpf_p4ndec256v32(_ptr(packed), packed.numel(), _ptr(offsets), n, int(bool(d1)),
                               ctypes.c_uint32(start0 & 0xFFFFFFFF), _ptr(out), _ptr(ws), ws.numel(), _ptr(err),
                               _stream(torch)))
@@ -644,9 +562,7 @@ def decn256v32_lists(packed, offsets, list_ptr, d1=False, start0=None, out=None,
     if out is None:
         out = torch.empty(int(list_ptr[-1].item()), dtype=torch.int32, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4ndec256v32_lists_workspace_size(nunits, nlists))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    ws = _ws(ws, packed.device, L.tpf_p4ndec256v32_lists_workspace_size, nunits, nlists)
     _check(L.tpf_p4ndec256v32_lists(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), nlists, int(bool(d1)),
                                     _ptr(start0), _ptr(out), out.numel(), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
@@ -688,9 +604,7 @@ def encn256v32_lists(values, list_ptr, d1=False, start0=None, nunits=None, out=N
     if offsets is None:
         offsets = torch.empty(nunits + 1, dtype=torch.int64, device=values.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4nenc256v32_lists_workspace_size(nunits, nlists))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=values.device)
+    ws = _ws(ws, values.device, L.tpf_p4nenc256v32_lists_workspace_size, nunits, nlists)
     _check(L.tpf_p4nenc256v32_lists(_ptr(values), values.numel(), _ptr(list_ptr), nlists, int(bool(d1)), _ptr(start0), _ptr(out),
                                     out.numel(), _ptr(offsets), nunits, _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     if trim:
@@ -712,9 +626,7 @@ def lists_unit_base(list_ptr, out=None, err=None, ws=None):
     if out is None:
         out = torch.empty(nlists + 1, dtype=torch.int32, device=list_ptr.device)
     L = lib()
-    ws_bytes = int(L.tpf_lists_unit_base_workspace_size(nlists))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=list_ptr.device)
+    ws = _ws(ws, list_ptr.device, L.tpf_lists_unit_base_workspace_size, nlists)
     _check(L.tpf_lists_unit_base(_ptr(list_ptr), nlists, _ptr(out), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
 
@@ -736,7 +648,6 @@ def decn256v32_lists_select(packed, offsets, list_ptr, list_unit, sel, d1=False,
     import torch
 
     nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
     nsel = sel.numel()
     if out is None:
         total = 0
@@ -749,12 +660,9 @@ def decn256v32_lists_select(packed, offsets, list_ptr, list_unit, sel, d1=False,
     if out_ptr is None:
         out_ptr = torch.empty(nsel + 1, dtype=torch.int64, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4ndec256v32_lists_select_workspace_size(nsel, out.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_p4ndec256v32_lists_select(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
-                                           int(bool(d1)), _ptr(start0), _ptr(sel), nsel, _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws),
-                                           ws.numel(), _ptr(err), _stream(torch)))
+    ws = _ws(ws, packed.device, L.tpf_p4ndec256v32_lists_select_workspace_size, nsel, out.numel())
+    _check(L.tpf_p4ndec256v32_lists_select(*_index(packed, offsets, list_ptr, list_unit), int(bool(d1)), _ptr(start0), _ptr(sel), nsel,
+                                           _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
 
 
@@ -775,9 +683,7 @@ def lists_unit_last(packed, offsets, list_ptr, start0=None, out=None, err=None, 
     if out is None:
         out = torch.empty(nunits, dtype=torch.int32, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_lists_unit_last_workspace_size(nunits, nlists))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
+    ws = _ws(ws, packed.device, L.tpf_lists_unit_last_workspace_size, nunits, nlists)
     _check(L.tpf_lists_unit_last(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), nlists, _ptr(start0), _ptr(out),
                                  _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
@@ -826,7 +732,6 @@ def decn256v32_lists_units(packed, offsets, list_ptr, list_unit, sel, ufirst, uc
     import torch
 
     nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
     nsel = sel.numel()
     if out is None:
         total = 0
@@ -844,16 +749,34 @@ def decn256v32_lists_units(packed, offsets, list_ptr, list_unit, sel, ufirst, uc
     if out_ptr is None:
         out_ptr = torch.empty(nsel + 1, dtype=torch.int64, device=packed.device)
     L = lib()
-    ws_bytes = int(L.tpf_p4ndec256v32_lists_units_workspace_size(nsel, out.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_p4ndec256v32_lists_units(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
-                                          int(bool(d1)), _ptr(start0), _ptr(unit_last), _ptr(sel), _ptr(ufirst), _ptr(ucount), nsel,
-                                          _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    ws = _ws(ws, packed.device, L.tpf_p4ndec256v32_lists_units_workspace_size, nsel, out.numel())
+    _check(L.tpf_p4ndec256v32_lists_units(*_index(packed, offsets, list_ptr, list_unit), int(bool(d1)), _ptr(start0), _ptr(unit_last),
+                                          _ptr(sel), _ptr(ufirst), _ptr(ucount), nsel, _ptr(out), out.numel(), _ptr(out_ptr), _ptr(ws),
+                                          ws.numel(), _ptr(err), _stream(torch)))
     return out, out_ptr
 
 
 # ---- intersection with a resident index (include/turbopfor_gpu.h tpf_lists_intersect) ----
+def _lists_probe(op, packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0, out, out_ptr, pidx, tpos, err, ws):
+    """The body of lists_intersect, lists_union and lists_difference: the
+    three entry points take the same arguments, and only the union's workspace
+    is sized by out as well."""
+    import torch
+
+    nq = qlist.numel()
+    if out is None:
+        out = torch.empty(probe.numel(), dtype=torch.int32, device=packed.device)
+    if out_ptr is None:
+        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    sized_by = (nq, probe.numel(), out.numel()) if op == "union" else (nq, probe.numel())
+    ws = _ws(ws, packed.device, getattr(L, f"tpf_lists_{op}_workspace_size"), *sized_by)
+    _check(getattr(L, f"tpf_lists_{op}")(*_index(packed, offsets, list_ptr, list_unit), _ptr(start0), _ptr(unit_last), _ptr(probe),
+                                         probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out), out.numel(), _ptr(out_ptr),
+                                         _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out, out_ptr
+
+
 def lists_intersect(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0=None, out=None, out_ptr=None,
                     pidx=None, tpos=None, err=None, ws=None):
     """Which probe doc ids are in their target lists: query k is the values
@@ -872,23 +795,8 @@ def lists_intersect(packed, offsets, list_ptr, list_unit, unit_last, probe, prob
     out's capacity, written when passed: the hit's index into probe and its
     position in the target list; err: optional int64 CUDA tensor [1] (-1 =
     clean).  Returns (out, out_ptr)."""
-    import torch
-
-    nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
-    nq = qlist.numel()
-    if out is None:
-        out = torch.empty(probe.numel(), dtype=torch.int32, device=packed.device)
-    if out_ptr is None:
-        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
-    L = lib()
-    ws_bytes = int(L.tpf_lists_intersect_workspace_size(nq, probe.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_lists_intersect(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
-                                 _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
-                                 out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
-    return out, out_ptr
+    return _lists_probe("intersect", packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0, out, out_ptr, pidx,
+                        tpos, err, ws)
 
 
 # ---- union with a resident index (include/turbopfor_gpu.h tpf_lists_union) ----
@@ -916,23 +824,10 @@ def lists_union(packed, offsets, list_ptr, list_unit, unit_last, probe, probe_pt
     LISTS_NONE otherwise; err: optional int64 CUDA tensor [1] (-1 = clean).
     The workspace is allocated here unless ws is large enough.  Asynchronous:
     no device-to-host read.  Returns (out, out_ptr)."""
-    import torch
-
     if out is None:
         raise ValueError("lists_union: out is required (its numel() is the capacity; sizing it here would read list_ptr back)")
-    nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
-    nq = qlist.numel()
-    if out_ptr is None:
-        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
-    L = lib()
-    ws_bytes = int(L.tpf_lists_union_workspace_size(nq, probe.numel(), out.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_lists_union(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
-                             _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
-                             out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
-    return out, out_ptr
+    return _lists_probe("union", packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0, out, out_ptr, pidx, tpos,
+                        err, ws)
 
 
 # ---- difference with a resident index (include/turbopfor_gpu.h tpf_lists_difference) ----
@@ -954,23 +849,8 @@ def lists_difference(packed, offsets, list_ptr, list_unit, unit_last, probe, pro
     first list value above it, or the list's length when there is none (not a
     lists_gather position); err: optional int64 CUDA tensor [1] (-1 = clean).
     Returns (out, out_ptr)."""
-    import torch
-
-    nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
-    nq = qlist.numel()
-    if out is None:
-        out = torch.empty(probe.numel(), dtype=torch.int32, device=packed.device)
-    if out_ptr is None:
-        out_ptr = torch.empty(nq + 1, dtype=torch.int64, device=packed.device)
-    L = lib()
-    ws_bytes = int(L.tpf_lists_difference_workspace_size(nq, probe.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_lists_difference(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists,
-                                  _ptr(start0), _ptr(unit_last), _ptr(probe), probe.numel(), _ptr(probe_ptr), _ptr(qlist), nq, _ptr(out),
-                                  out.numel(), _ptr(out_ptr), _ptr(pidx), _ptr(tpos), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
-    return out, out_ptr
+    return _lists_probe("difference", packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0, out, out_ptr, pidx,
+                        tpos, err, ws)
 
 
 # ---- values at list positions of a resident index (include/turbopfor_gpu.h tpf_lists_gather) ----
@@ -995,18 +875,13 @@ def lists_gather(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, d1=F
 
     if d1 and unit_last is None:
         raise ValueError("lists_gather: d1=True needs unit_last (lists_unit_last)")
-    nlists = list_ptr.numel() - 1
-    nunits = offsets.numel() - 1
     nq = qlist.numel()
     if out is None:
         out = torch.empty_like(pos)
     L = lib()
-    ws_bytes = int(L.tpf_lists_gather_workspace_size(nq, pos.numel()))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=packed.device)
-    _check(L.tpf_lists_gather(_ptr(packed), packed.numel(), _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
-                              _ptr(start0), _ptr(unit_last), _ptr(pos), pos.numel(), _ptr(pos_ptr), _ptr(qlist), nq, _ptr(out), _ptr(ws),
-                              ws.numel(), _ptr(err), _stream(torch)))
+    ws = _ws(ws, packed.device, L.tpf_lists_gather_workspace_size, nq, pos.numel())
+    _check(L.tpf_lists_gather(*_index(packed, offsets, list_ptr, list_unit), int(bool(d1)), _ptr(start0), _ptr(unit_last), _ptr(pos),
+                              pos.numel(), _ptr(pos_ptr), _ptr(qlist), nq, _ptr(out), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
     return out
 
 
@@ -1040,6 +915,27 @@ def lists_item_cap(device, run=LISTS_IX_RUN):
     workgroup, `run` items per wave): a request of more items makes every wave
     stride."""
     return LISTS_MIN_W * _lists_cus(device) * 4 * run
+
+
+def _index_out(dev, nlists_out, d1, out, out_offsets, units_cap, units_bound, bytes_bound):
+    """The output side lists_append and lists_remove share: the caller's out /
+    out_offsets / units_cap or their defaults (units_bound() and bytes_bound()
+    are asked only for a default), and the new index's fresh list_ptr,
+    list_unit and -- with d1 -- unit_last.  Returns the five tensors the call
+    returns, and their arguments in the entry points' order."""
+    import torch
+
+    if units_cap is None:
+        units_cap = out_offsets.numel() - 1 if out_offsets is not None else units_bound()
+    if out_offsets is None:
+        out_offsets = torch.empty(units_cap + 1, dtype=torch.int64, device=dev)
+    if out is None:
+        out = torch.empty(max(bytes_bound(), 1), dtype=torch.uint8, device=dev)
+    list_ptr_out = torch.empty(nlists_out + 1, dtype=torch.int64, device=dev)
+    list_unit_out = torch.empty(nlists_out + 1, dtype=torch.int32, device=dev)
+    unit_last_out = torch.empty(max(units_cap, 1), dtype=torch.int32, device=dev) if d1 else None
+    return ((out, out_offsets, list_ptr_out, list_unit_out, unit_last_out),
+            (_ptr(out), out.numel(), _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out)))
 
 
 def lists_append_units_bound(nunits, nlists_out, add_values):
@@ -1086,23 +982,13 @@ def lists_append(packed, offsets, list_ptr, list_unit, add, add_ptr, d1=False, s
     nlists_out = add_ptr.numel() - 1
     nadd = add.numel() if add is not None else 0
     L = lib()
-    if units_cap is None:
-        units_cap = out_offsets.numel() - 1 if out_offsets is not None else lists_append_units_bound(nunits, nlists_out, nadd)
-    if out_offsets is None:
-        out_offsets = torch.empty(units_cap + 1, dtype=torch.int64, device=dev)
-    if out is None:
-        out = torch.empty(max(lists_append_bound(in_bytes, nlists_out, nadd), 1), dtype=torch.uint8, device=dev)
-    list_ptr_out = torch.empty(nlists_out + 1, dtype=torch.int64, device=dev)
-    list_unit_out = torch.empty(nlists_out + 1, dtype=torch.int32, device=dev)
-    unit_last_out = torch.empty(max(units_cap, 1), dtype=torch.int32, device=dev) if d1 else None
-    ws_bytes = int(L.tpf_lists_append_workspace_size(nunits, nlists_out, nadd))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    res, res_args = _index_out(dev, nlists_out, d1, out, out_offsets, units_cap, lambda: lists_append_units_bound(nunits, nlists_out, nadd),
+                               lambda: lists_append_bound(in_bytes, nlists_out, nadd))
+    ws = _ws(ws, dev, L.tpf_lists_append_workspace_size, nunits, nlists_out, nadd)
     _check(L.tpf_lists_append(_ptr(packed), in_bytes, _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
-                              _ptr(start0), _ptr(unit_last), _ptr(add), nadd, _ptr(add_ptr), nlists_out, _ptr(out), out.numel(),
-                              _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out), _ptr(ws),
-                              ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
-    return out, out_offsets, list_ptr_out, list_unit_out, unit_last_out
+                              _ptr(start0), _ptr(unit_last), _ptr(add), nadd, _ptr(add_ptr), nlists_out, *res_args, _ptr(ws), ws.numel(),
+                              _ptr(err), stream if stream is not None else _stream(torch)))
+    return res
 
 
 # ---- postings deleted from a resident index (include/turbopfor_gpu.h tpf_lists_remove) ----
@@ -1145,20 +1031,10 @@ def lists_remove(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, stag
     npos = pos.numel() if pos is not None else 0
     stage_values = int(stage_values)
     L = lib()
-    if units_cap is None:
-        units_cap = out_offsets.numel() - 1 if out_offsets is not None else nunits
-    if out_offsets is None:
-        out_offsets = torch.empty(units_cap + 1, dtype=torch.int64, device=dev)
-    if out is None:
-        out = torch.empty(max(lists_remove_bound(in_bytes, nq, stage_values), 1), dtype=torch.uint8, device=dev)
-    list_ptr_out = torch.empty(nlists + 1, dtype=torch.int64, device=dev)
-    list_unit_out = torch.empty(nlists + 1, dtype=torch.int32, device=dev)
-    unit_last_out = torch.empty(max(units_cap, 1), dtype=torch.int32, device=dev) if d1 else None
-    ws_bytes = int(L.tpf_lists_remove_workspace_size(nunits, nlists, nq, npos, stage_values))
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    res, res_args = _index_out(dev, nlists, d1, out, out_offsets, units_cap, lambda: nunits,
+                               lambda: lists_remove_bound(in_bytes, nq, stage_values))
+    ws = _ws(ws, dev, L.tpf_lists_remove_workspace_size, nunits, nlists, nq, npos, stage_values)
     _check(L.tpf_lists_remove(_ptr(packed), in_bytes, _ptr(offsets), nunits, _ptr(list_ptr), _ptr(list_unit), nlists, int(bool(d1)),
-                              _ptr(start0), _ptr(unit_last), _ptr(pos), npos, _ptr(pos_ptr), _ptr(qlist), nq, stage_values, _ptr(out),
-                              out.numel(), _ptr(out_offsets), units_cap, _ptr(list_ptr_out), _ptr(list_unit_out), _ptr(unit_last_out),
+                              _ptr(start0), _ptr(unit_last), _ptr(pos), npos, _ptr(pos_ptr), _ptr(qlist), nq, stage_values, *res_args,
                               _ptr(ws), ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
-    return out, out_offsets, list_ptr_out, list_unit_out, unit_last_out
+    return res
