@@ -88,6 +88,28 @@ uint64_t tpf_block_size(int fmt, const uint8_t *in, uint64_t avail, unsigned n, 
 /* Offsets of nblocks consecutive blocks (off[nblocks] = total).  Returns the
  * total byte length, or -(i+1) if block i is malformed/truncated. */
 int64_t tpf_scan_offsets(int fmt, const uint8_t *in, uint64_t in_bytes, unsigned n, uint64_t nblocks, uint64_t *off);
+/* Unit offsets of a LISTS stream (tpf_p4nenc256v32_lists, or a reference
+ * caller's p4(D1)Enc256v32 / p4(D1)Enc32 loop over every list): list j holds n_j =
+ * list_ptr[j+1] - list_ptr[j] values in n_j/256 p4Enc256v32 blocks and one
+ * p4Enc32 tail of n_j%256 values, and nunits is the sum of the lists' unit
+ * counts.  This is the sequential definition tpf_lists_unit_offsets
+ * (turbopfor_gpu.h) is held to, offset for offset and code for code.
+ *   - list_byte == NULL: the lists lie end to end from byte 0, every unit may
+ *     reach to in_bytes, and off[nunits] is the stream's length.  The walk
+ *     stops at the first bad unit.
+ *   - list_byte given (nlists + 1 entries, e.g. a term dictionary's byte
+ *     positions): list j occupies exactly [list_byte[j], list_byte[j+1]); a
+ *     unit is held to the rest of that span and the last unit of a list must
+ *     end it.  In a list with a bad unit the units after it get list_byte[j+1];
+ *     every other list is complete.  off[nunits] = list_byte[nlists].
+ * Returns off[nunits], or -(code + 1): code < nunits the lowest bad unit;
+ * nunits + j the first list with ptr[j+1] < ptr[j], byte[j+1] < byte[j],
+ * byte[j+1] > in_bytes or no values in a non-empty span; nunits + nlists the
+ * unit counts do not add up to nunits.  The last two write nothing.  nlists ==
+ * 0 writes off[0] = 0. */
+int64_t tpf_lists_scan_offsets(const uint8_t *in, uint64_t in_bytes, const uint64_t *list_ptr, uint64_t nlists,
+                               const uint64_t *list_byte /* nlists + 1, or NULL */, uint64_t *off /* nunits + 1 */,
+                               uint64_t nunits);
 /* Caller-supplied offsets (off[0..nblocks]): 0 when they never decrease and
  * off[nblocks] <= in_bytes; -(i+1) when off[i] > off[i+1]; -(nblocks+1) when
  * the last offset is past in_bytes (-1 for a NULL array).  The host streams

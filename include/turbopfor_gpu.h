@@ -463,6 +463,70 @@ int tpf_lists_unit_last(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *
                         const uint64_t *d_list_ptr, uint64_t nlists, const uint32_t *d_start0,
                         uint32_t *d_unit_last /* nunits */, void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- opening a stream that has no offsets -------------------------------------
+ * The reference writes no offsets, and an index built with it is a postings
+ * file plus a term dictionary: per list a byte position and a count, nothing
+ * per unit.  tpf_lists_unit_offsets rebuilds d_off[0..nunits] of such a stream
+ * on the device from the lists' byte spans and the units' own headers, so that
+ * with tpf_lists_unit_base and tpf_lists_unit_last every table of a resident
+ * index can be rebuilt there.  Its sequential definition is
+ * tpf_lists_scan_offsets (turbopfor_capi.h): the two agree offset for offset
+ * and code for code.
+ *   - Input: d_list_ptr (nlists + 1, non-decreasing; only differences are
+ *     used: n_j = ptr[j+1] - ptr[j]) and d_list_byte (nlists + 1,
+ *     non-decreasing, d_list_byte[nlists] <= in_bytes; d_list_byte[0] need not
+ *     be 0).  List j's stream is exactly the bytes [d_list_byte[j],
+ *     d_list_byte[j+1]) of d_in: n_j/256 p4Enc256v32 blocks and one p4Enc32
+ *     tail of n_j%256 values.  Lists are contiguous, as every entry point
+ *     above requires; an empty list has an empty span.  d_in may start at any
+ *     byte address.
+ *   - Output: d_off[d_list_unit[j] + i] is the byte offset of unit i of list j
+ *     and d_off[nunits] = d_list_byte[nlists] (nunits + 1 entries, written).
+ *     d_list_unit (optional, nlists + 1 entries) is what tpf_lists_unit_base
+ *     writes.  The result feeds every lists entry point unchanged, on the same
+ *     stream; for a stream written by tpf_p4nenc256v32_lists it is the
+ *     encoder's d_off shifted by d_list_byte[0].
+ *   - What is parsed: every unit's length, from its header bytes by the rules
+ *     of tpf_block_size, refusals included (b > 32, bx > 32, a constant wider
+ *     than 4 bytes in a tail, truncation), held to the rest of its list's
+ *     span; the last unit of a list must end exactly at d_list_byte[j+1].  No
+ *     base payload is read: headers, exception bitmaps and vbyte marker bytes
+ *     only.
+ *   - Bounds: nothing at or past d_in + in_bytes can change a result; the
+ *     values of d_list_ptr and d_list_byte are checked, never followed; nothing
+ *     is written outside d_off[0..nunits] and d_list_unit[0..nlists].
+ *   - Errors through d_err (optional; UINT64_MAX = clean), the lowest code:
+ *       < nunits        the lowest unit whose parsed length is 0 (malformed, or
+ *                       past its list's span) or, for a list's last unit,
+ *                       differs from what is left of the span.  Every other
+ *                       list is complete and correct; in the offending list the
+ *                       units after the bad one get d_list_byte[j+1], which is
+ *                       in bounds and non-decreasing;
+ *       nunits + j      the first list j with ptr[j+1] < ptr[j], byte[j+1] <
+ *                       byte[j], byte[j+1] > in_bytes, or n_j == 0 with a
+ *                       non-empty span: nothing is written;
+ *       nunits + nlists the unit counts do not add up to nunits: nothing is
+ *                       written.
+ *   - TPF_EINVAL (decided before any device call): nunits or nlists above
+ *     0x7FFFFFFF; a null d_off; with nlists non-zero a null d_list_ptr,
+ *     d_list_byte or d_ws, or ws_bytes below
+ *     tpf_lists_unit_offsets_workspace_size(nunits, nlists); a null d_in with
+ *     nunits non-zero.  nlists == 0 is a successful no-op that writes d_off[0]
+ *     = 0 and sets d_err to clean.
+ *   - Workspace: under the WORKSPACE CONTRACT above (the export is a multiple
+ *     of 256 and non-decreasing in both counts).
+ *   - Cost: parallel across lists; inside a list the walk is a dependent chain
+ *     of one step per unit, so the longest list sets a latency floor (DESIGN.md
+ *     4.21).  A list of one unit needs no walk.
+ *   - Everything is enqueued on `stream`: no host synchronisation, no
+ *     device-to-host copy, a number of launches fixed by the arguments' sizes;
+ *     the call can be captured into a hipGraph. */
+size_t tpf_lists_unit_offsets_workspace_size(uint64_t nunits, uint64_t nlists);
+int tpf_lists_unit_offsets(const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_list_ptr,
+                           const uint64_t *d_list_byte /* nlists + 1 */, uint64_t nlists, uint64_t *d_off /* nunits + 1 */,
+                           uint64_t nunits, uint32_t *d_list_unit /* nlists + 1, optional */, void *d_ws, size_t ws_bytes,
+                           uint64_t *d_err, void *stream);
+
 /* tpf_lists_range_units answers nq range queries over the skip table: query k
  * asks for the units of list j = d_qlist[k] that can hold a value in
  * [d_qlo[k], d_qhi[k]], both ends inclusive.

@@ -584,6 +584,27 @@ int tpf_lists_unit_base(const uint64_t * d_list_ptr, uint64_t nlists, uint32_t *
     return done(tpf::launch_lists_unit_base(d_list_ptr, nlists, d_list_unit, d_ws, dev_err(d_err), s), "tpf_lists_unit_base");
 }
 
+// ---- the way in for a stream without offsets: the unit offsets from the
+// lists' byte spans and the units' headers.
+size_t tpf_lists_unit_offsets_workspace_size(uint64_t nunits, uint64_t nlists) { return tpf::lists_unit_offsets_workspace(nunits, nlists); }
+
+int tpf_lists_unit_offsets(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_list_ptr, const uint64_t * d_list_byte,
+                           uint64_t nlists, uint64_t * d_off, uint64_t nunits, uint32_t * d_list_unit, void * d_ws, size_t ws_bytes,
+                           uint64_t * d_err, void * stream)
+{
+    if (over_limit({nunits, nlists}))
+        return fail(TPF_EINVAL, "tpf_lists_unit_offsets: nunits and nlists are limited to 0x7FFFFFFF");
+    if (!d_off || (nlists && (!d_list_ptr || !d_list_byte || !d_ws)) || (nunits && !d_in))
+        return fail(TPF_EINVAL, "tpf_lists_unit_offsets: null pointer");
+    if (nlists && ws_bytes < tpf_lists_unit_offsets_workspace_size(nunits, nlists))
+        return fail(TPF_EINVAL, "tpf_lists_unit_offsets: workspace too small");
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
+        return rc;
+    return done(tpf::launch_lists_unit_offsets(d_in, in_bytes, d_list_ptr, d_list_byte, nlists, d_off, nunits, d_list_unit, d_ws,
+                                               dev_err(d_err), s), "tpf_lists_unit_offsets");
+}
+
 size_t tpf_p4ndec256v32_lists_select_workspace_size(uint64_t nsel, uint64_t out_values)
 {
     return tpf::lists_select_workspace(nsel, out_values);

@@ -181,4 +181,65 @@ int64_t tpf_scan_offsets(int fmt, const uint8_t * in, uint64_t in_bytes, unsigne
     return static_cast<int64_t>(pos);
 }
 
+// A lists stream (tpf_p4nenc256v32_lists): list j is n_j / 256 p4Enc256v32
+// blocks and one p4Enc32 tail of n_j % 256 values.  The sequential definition
+// of tpf_lists_unit_offsets (p4_lists_scan.hip), codes and what is written
+// included.
+int64_t tpf_lists_scan_offsets(const uint8_t * in, uint64_t in_bytes, const uint64_t * list_ptr, uint64_t nlists,
+                               const uint64_t * list_byte, uint64_t * off, uint64_t nunits)
+{
+    const auto code = [](uint64_t c) { return -static_cast<int64_t>(c) - 1; };
+    if (nlists == 0)
+    {
+        off[0] = 0;
+        return 0;
+    }
+    // structure first: a refusal writes nothing
+    uint64_t total = 0;
+    for (uint64_t j = 0; j < nlists; ++j)
+    {
+        if (list_ptr[j + 1] < list_ptr[j])
+            return code(nunits + j);
+        const uint64_t n = list_ptr[j + 1] - list_ptr[j];
+        if (list_byte
+            && (list_byte[j + 1] < list_byte[j] || list_byte[j + 1] > in_bytes || (n == 0 && list_byte[j + 1] != list_byte[j])))
+            return code(nunits + j);
+        total += n / 256u + (n % 256u != 0u);
+    }
+    if (total != nunits)
+        return code(nunits + nlists);
+
+    uint64_t u = 0, pos = list_byte ? list_byte[0] : 0u, bad = ~0ull;
+    int cst = 0;
+    for (uint64_t j = 0; j < nlists; ++j)
+    {
+        const uint64_t n = list_ptr[j + 1] - list_ptr[j];
+        const uint64_t units = n / 256u + (n % 256u != 0u);
+        const uint64_t end = list_byte ? list_byte[j + 1] : in_bytes;
+        if (list_byte)
+            pos = list_byte[j];
+        for (uint64_t i = 0; i < units; ++i, ++u)
+        {
+            off[u] = pos;
+            const bool full = i < n / 256u;
+            const uint64_t avail = end - pos;
+            uint64_t sz = one_block(full ? TPF_FMT_256V32 : TPF_FMT_32, in + pos, avail, full ? 256u : static_cast<uint32_t>(n % 256u), &cst);
+            if (list_byte && i + 1 == units && sz != avail)
+                sz = 0; // the last unit ends its list's span
+            if (sz == 0)
+            {
+                if (!list_byte)
+                    return code(u); // no anchor to go on from
+                bad = bad < u ? bad : u;
+                for (++i, ++u; i < units; ++i, ++u)
+                    off[u] = end;
+                break;
+            }
+            pos += sz;
+        }
+    }
+    off[nunits] = list_byte ? list_byte[nlists] : pos;
+    return bad != ~0ull ? code(bad) : static_cast<int64_t>(off[nunits]);
+}
+
 } // extern "C"

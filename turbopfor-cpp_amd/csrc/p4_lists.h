@@ -280,6 +280,15 @@ hipError_t launch_lists_remove(const ListsIndex & X, bool d1, const uint32_t * p
                                const uint32_t * qlist, uint64_t nq, uint64_t stage_values, uint8_t * out, uint64_t out_cap,
                                uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out,
                                void * ws, unsigned long long * err, hipStream_t s);
+// the unit offsets of a stream that has none, from the lists' byte spans and
+// the units' headers (p4_lists_scan.hip).  Passes: plan (one
+// thread per list: the checks, its unit count) -> run scan -> short (the
+// verdict, the unit directory, the one-unit lists) -> walk (a wave per list of
+// two or more units).  The workspace is sized by nlists alone.
+size_t lists_unit_offsets_workspace(uint64_t nunits, uint64_t nlists);
+hipError_t launch_lists_unit_offsets(const uint8_t * in, uint64_t in_bytes, const uint64_t * ptr, const uint64_t * lbyte, uint64_t nlists,
+                                     uint64_t * off, uint64_t nunits, uint32_t * list_unit, void * ws, unsigned long long * err,
+                                     hipStream_t s);
 // phase A over a lists stream (p4_dec256v32.hip): block sums + run scan into
 // `ws` (the chained decode's layout, d1chain_workspace(nunits) bytes), tail
 // units skipped; *view = where phase B finds them

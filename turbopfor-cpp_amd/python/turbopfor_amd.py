@@ -756,6 +756,68 @@ def decn256v32_lists_units(packed, offsets, list_ptr, list_unit, sel, ufirst, uc
     return out, out_ptr
 
 
+# ---- opening a stream without offsets (include/turbopfor_gpu.h tpf_lists_unit_offsets,
+# include/turbopfor_capi.h tpf_lists_scan_offsets) ----
+LISTS_SCAN_RUN = 16     # kScanRun (csrc/p4_lists_scan.hip): lists per wave of the walk
+LISTS_SCAN_WINDOW = 1024  # kScanWin: bytes of the stream the walker holds in LDS
+
+
+def lists_unit_offsets(packed, list_ptr, list_byte, nunits=None, out=None, list_unit=None, err=None, ws=None):
+    """The unit offsets of a lists stream that has none, on the device, once
+    per index: out[list_unit[j] + i] = the byte offset of unit i of list j and
+    out[nunits] = list_byte[nlists], from the lists' byte spans and the units'
+    own headers.  packed: uint8 CUDA tensor; list_ptr / list_byte: int64 CUDA
+    tensors [nlists + 1] -- list j holds list_ptr[j+1] - list_ptr[j] values in
+    the bytes [list_byte[j], list_byte[j+1]) of packed.  nunits: the stream's
+    unit count (default: from out, else computed from list_ptr with
+    lists_units, which costs a device-to-host read).  out: int64 CUDA tensor
+    [nunits + 1]; list_unit: optional int32 CUDA tensor [nlists + 1], written
+    as lists_unit_base writes it; err: optional int64 CUDA tensor [1] (-1 =
+    clean; the codes of tpf_lists_unit_offsets).  Asynchronous when nunits or
+    out is given.  Returns out."""
+    import torch
+
+    nlists = list_ptr.numel() - 1
+    if nunits is None:
+        nunits = out.numel() - 1 if out is not None else int(lists_units(list_ptr)[1][-1])
+    if out is None:
+        out = torch.empty(nunits + 1, dtype=torch.int64, device=packed.device)
+    L = lib()
+    ws = _ws(ws, packed.device, L.tpf_lists_unit_offsets_workspace_size, nunits, nlists)
+    _check(L.tpf_lists_unit_offsets(_ptr(packed), packed.numel(), _ptr(list_ptr), _ptr(list_byte), nlists, _ptr(out), nunits,
+                                    _ptr(list_unit), _ptr(ws), ws.numel(), _ptr(err), _stream(torch)))
+    return out
+
+
+def lists_scan_offsets_host(packed, list_ptr, list_byte=None, nunits=None):
+    """The same on the host, sequentially (tpf_lists_scan_offsets): the
+    definition lists_unit_offsets is held to, which also serves a stream
+    without per-list anchors.  packed: bytes or a uint8 numpy array; list_ptr:
+    nlists + 1 integers; list_byte: nlists + 1 integers, or None for lists that
+    lie end to end from byte 0.  Returns (offsets, code): offsets an int64
+    numpy array [nunits + 1], code -1 when clean, else the call's code."""
+    import numpy as np
+
+    buf = np.frombuffer(packed, dtype=np.uint8) if isinstance(packed, (bytes, bytearray, memoryview)) else np.ascontiguousarray(packed, np.uint8)
+    ptr = np.ascontiguousarray(list_ptr, dtype=np.uint64)
+    lb = None if list_byte is None else np.ascontiguousarray(list_byte, dtype=np.uint64)
+    if nunits is None:
+        nunits = int(lists_units(np.asarray(list_ptr))[1][-1])
+    off = np.zeros(nunits + 1, dtype=np.uint64)
+    r = lib().tpf_lists_scan_offsets(buf.ctypes.data, buf.size, ptr.ctypes.data, ptr.size - 1, None if lb is None else lb.ctypes.data,
+                                     off.ctypes.data, nunits)
+    return off.astype(np.int64), (-1 if r >= 0 else -r - 1)
+
+
+def lists_list_byte(offsets, list_unit):
+    """list_byte of a resident index: offsets[list_unit[j]] for j = 0 ..
+    nlists, the first byte of every list and the stream's end -- what a saver
+    keeps when it drops the 8 bytes per unit of offsets, and what
+    lists_unit_offsets takes to rebuild them.  A torch gather on the tensors'
+    device."""
+    return offsets[list_unit.long()]
+
+
 # ---- intersection with a resident index (include/turbopfor_gpu.h tpf_lists_intersect) ----
 def _lists_probe(op, packed, offsets, list_ptr, list_unit, unit_last, probe, probe_ptr, qlist, start0, out, out_ptr, pidx, tpos, err, ws):
     """The body of lists_intersect, lists_union and lists_difference: the
