@@ -1162,6 +1162,110 @@ int tpf_lists_remove(
                         uint32_t *d_unit_last_out /* units_cap; required when d1 != 0 */,
                         void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
 
+/* ---- a sub-index of a resident index -------------------------------------------
+ * tpf_lists_extract takes a lists stream apart: list k of the result is a unit
+ * range of list d_sel[k] of the index, and the result is an index of its own --
+ * stream, unit offsets, both directories, the delta-1 starts and the skip table
+ * out of one call.  A unit's bytes depend on its values and the value before it
+ * only, so a unit range of a list is the encoder's own stream for the values of
+ * that range: the bytes are moved, nothing is parsed, decoded or encoded.  A
+ * term shard (the lists with j % world == rank), a doc-id window (the ranges of
+ * tpf_lists_range_units), the lists that stay resident after an eviction and the
+ * part of an index that is saved or shipped are each one call.
+ *   - The index: as tpf_p4ndec256v32_lists_units reads it.  d_start0 has nlists
+ *     entries (NULL = 0).  With d1 == 0, d_start0, d_unit_last, d_start0_out and
+ *     d_unit_last_out are ignored.  With nunits == 0 d_in and d_off are not read.
+ *   - The selection: list k of the result is units [d_ufirst[k], d_ufirst[k] +
+ *     d_ucount[k]) of list j = d_sel[k], list-relative; with d_ufirst == NULL it
+ *     is all of list j and d_ucount is not read.  These are the arguments of
+ *     tpf_p4ndec256v32_lists_units: d_qlist, d_ufirst and d_ucount of
+ *     tpf_lists_range_units feed the call unchanged, on the same stream.
+ *     Selections come in any order and may repeat; each occurrence gets a copy of
+ *     its own.  Empty lists and d_ucount[k] == 0 are allowed anywhere, any number
+ *     in a row, d_ufirst[k] == the list's unit count with a zero count included.
+ *   - The result: list k has 256 * ucount values, or 256 * (ucount - 1) + n_j %
+ *     256 when the range reaches the list's tail unit.  d_list_ptr_out[0] = 0;
+ *     d_list_unit_out is what tpf_lists_unit_base gives for the result, its last
+ *     entry the result's unit count nunits_out.  A unit range is a well-formed
+ *     list: full blocks, then the tail at most once, at the end.
+ *   - Delta-1 starts: d_start0_out[k] = d_start0[j] (0 for NULL) when the range
+ *     starts the list (d_ufirst[k] == 0 or d_ufirst == NULL), else the skip
+ *     table's entry of the unit before it, d_unit_last[d_list_unit[j] +
+ *     d_ufirst[k] - 1].  d_unit_last is therefore required when d1 != 0 and
+ *     d_ufirst != NULL and optional otherwise.  d_unit_last_out is written
+ *     exactly when d1 != 0 and both d_unit_last and d_unit_last_out are non-null:
+ *     the source entries of the copied units, which is what tpf_lists_unit_last
+ *     gives for the new stream.  The frequency stream stored in parallel over
+ *     the same directory is extracted by the same selection with d1 == 0.
+ *   - Bytes: d_out is the selected units' bytes laid end to end in selection
+ *     order, d_off_out[u] = (first output byte of list k) + d_off[src(u)] -
+ *     d_off[src of k's first unit], d_off_out[0] = 0 and d_off_out[nunits_out]
+ *     the stream's length.  For an index written by this library's encoders
+ *     d_out and d_off_out are byte for byte and offset for offset what
+ *     tpf_p4nenc256v32_lists writes for the selected values with d1 and
+ *     d_start0_out; for any stream that passes the checks the result decodes to
+ *     the selected values.  Interior offsets are carried over shifted and not
+ *     checked; the two ends of each copied range are held against each other and
+ *     against in_bytes.  The table holds values, never indices: a wrong table
+ *     gives wrong starts and never an out-of-range access.  The outputs must not
+ *     overlap the inputs.
+ *   - Capacities: units_cap is the capacity of d_off_out (units_cap + 1 entries)
+ *     and of d_unit_last_out, out_cap that of d_out.  Nothing is written at or
+ *     past a capacity.  With repeats the result can be larger than the index, so
+ *     there is no bound from the sizes alone: a call with out_cap == 0 and d_out
+ *     == NULL is the sizing call (the last code below).
+ *   - Errors through d_err (optional; UINT64_MAX = clean); the values are
+ *     checked, never followed; the lowest code is the one reported.  Nothing is
+ *     parsed, so no code below nunits is ever reported:
+ *       nunits + k         the first refused selection k: d_sel[k] >= nlists;
+ *                          list_ptr[j+1] < list_ptr[j]; a d_list_unit span
+ *                          different from the unit count of n_j; list_unit[j+1] >
+ *                          nunits; ufirst + ucount (summed without 32-bit wrap)
+ *                          above the list's unit count; a copied byte range with
+ *                          off[lo] > off[hi] or off[hi] > in_bytes.  Nothing is
+ *                          written, in any output;
+ *       nunits + nsel      nunits_out > units_cap or nunits_out > 0x7FFFFFFF:
+ *                          only d_list_ptr_out, d_list_unit_out and, with d1,
+ *                          d_start0_out are written, completely;
+ *       nunits + nsel + 1  the stream is longer than out_cap: everything is
+ *                          written except d_out, so d_off_out[nunits_out] is
+ *                          what to allocate.
+ *   - TPF_EINVAL (decided before any device call): a null d_off_out,
+ *     d_list_ptr_out or d_list_unit_out; with nsel non-zero a null d_sel,
+ *     d_list_ptr, d_list_unit or d_ws, a null d_out with out_cap non-zero, a null
+ *     d_in or d_off with nunits non-zero, a null d_ucount with d_ufirst non-null,
+ *     a null d_start0_out with d1 != 0, a null d_unit_last with d1 != 0 and
+ *     d_ufirst non-null; ws_bytes below tpf_lists_extract_workspace_size(nsel);
+ *     nunits, nlists, nsel or units_cap above 0x7FFFFFFF.  nsel == 0 is a
+ *     successful no-op that writes d_list_ptr_out[0] = 0, d_list_unit_out[0] = 0,
+ *     d_off_out[0] = 0 and a clean d_err.
+ *   - Workspace: O(nsel), under the WORKSPACE CONTRACT above (the export is a
+ *     multiple of 256 and non-decreasing in nsel).
+ *   - Cost: no kernel is sized by nlists, nunits or in_bytes.  The plan and the
+ *     workspace are sized by nsel, the offsets pass by units_cap and the move by
+ *     out_cap, on the host; waves past the real totals exit.  Nothing of the
+ *     index is read at a list or unit that is not selected, but for the [j+1]
+ *     directory entries, the end offset of a selected range and, with d1,
+ *     d_unit_last of the unit before a range.  Everything is enqueued on
+ *     `stream`: no host synchronisation and no device-to-host copy, so the call
+ *     can be captured into a hipGraph; 12 launches at the most (d_err's reset,
+ *     the header's, the plan, 3 x 2 run scans, the heads, the offsets unless
+ *     units_cap == 0, the move unless out_cap == 0; two with nsel == 0), their
+ *     number and their grids fixed by the arguments' sizes, not their contents.
+ * d_ws: device workspace, at least 8-byte aligned. */
+size_t tpf_lists_extract_workspace_size(uint64_t nsel);
+int tpf_lists_extract(
+    /* the index */     const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t nunits,
+                        const uint64_t *d_list_ptr, const uint32_t *d_list_unit, uint64_t nlists,
+                        int d1, const uint32_t *d_start0 /* nlists, or NULL = 0 */, const uint32_t *d_unit_last,
+    /* the selection */ const uint32_t *d_sel, const uint32_t *d_ufirst /* NULL: whole lists */,
+                        const uint32_t *d_ucount /* read only with d_ufirst */, uint64_t nsel,
+    /* the new index */ uint8_t *d_out, uint64_t out_cap, uint64_t *d_off_out /* units_cap + 1 */, uint64_t units_cap,
+                        uint64_t *d_list_ptr_out /* nsel + 1 */, uint32_t *d_list_unit_out /* nsel + 1 */,
+                        uint32_t *d_start0_out /* nsel; required when d1 != 0 */,
+                        uint32_t *d_unit_last_out /* units_cap; optional */,
+                        void *d_ws, size_t ws_bytes, uint64_t *d_err, void *stream);
+
 /* ---- host pipeline utility ----------------------------------------------
  * Copies `bytes` bytes with a kernel (16-byte non-temporal stores) instead of
  * an SDMA engine; either side may be pinned/registered host memory, at any

@@ -808,7 +808,7 @@ int tpf_lists_gather(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
 }
 
 // ---- postings appended to a resident index (p4_lists_append.hip)
-// A null pointer of the output side, which tpf_lists_append and tpf_lists_remove share, for a result of n lists: the
+// A null pointer of the output side, which tpf_lists_append, tpf_lists_remove and tpf_lists_extract share, for a result of n lists: the
 // three directories written always; the workspace, and d_out when it has a capacity, once there are lists.
 static bool index_out_null(uint64_t n, const uint8_t * d_out, uint64_t out_cap, const uint64_t * d_off_out, const uint64_t * d_list_ptr_out,
                            const uint32_t * d_list_unit_out, const void * d_ws)
@@ -906,6 +906,40 @@ int tpf_lists_remove(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d
     return done(tpf::launch_lists_remove(X, d1 != 0, d_pos, pos_values, d_pos_ptr, d_qlist, nlists ? nq : 0u, stage_values, d_out, out_cap,
                                          d_off_out, units_cap, d_list_ptr_out, d_list_unit_out, d1 ? d_unit_last_out : nullptr, d_ws,
                                          dev_err(d_err), s), "tpf_lists_remove");
+}
+
+// ---- a sub-index of a resident index (p4_lists_extract.hip)
+size_t tpf_lists_extract_workspace_size(uint64_t nsel) { return tpf::lists_extract_workspace(nsel); }
+
+int tpf_lists_extract(const uint8_t * d_in, uint64_t in_bytes, const uint64_t * d_off, uint64_t nunits, const uint64_t * d_list_ptr,
+                      const uint32_t * d_list_unit, uint64_t nlists, int d1, const uint32_t * d_start0, const uint32_t * d_unit_last,
+                      const uint32_t * d_sel, const uint32_t * d_ufirst, const uint32_t * d_ucount, uint64_t nsel, uint8_t * d_out,
+                      uint64_t out_cap, uint64_t * d_off_out, uint64_t units_cap, uint64_t * d_list_ptr_out, uint32_t * d_list_unit_out,
+                      uint32_t * d_start0_out, uint32_t * d_unit_last_out, void * d_ws, size_t ws_bytes, uint64_t * d_err, void * stream)
+{
+    if (over_limit({nunits, nlists, nsel, units_cap}))
+        return fail(TPF_EINVAL, "tpf_lists_extract: nunits, nlists, nsel and units_cap are limited to 0x7FFFFFFF");
+    if (index_out_null(nsel, d_out, out_cap, d_off_out, d_list_ptr_out, d_list_unit_out, d_ws)
+        || (nsel && (!d_sel || !d_list_ptr || !d_list_unit)))
+        return fail(TPF_EINVAL, "tpf_lists_extract: null pointer");
+    if (nsel && nunits && (!d_in || !d_off))
+        return fail(TPF_EINVAL, "tpf_lists_extract: null pointer (the index)");
+    if (nsel && d_ufirst && !d_ucount)
+        return fail(TPF_EINVAL, "tpf_lists_extract: null d_ucount with d_ufirst");
+    if (nsel && d1 && !d_start0_out)
+        return fail(TPF_EINVAL, "tpf_lists_extract: null d_start0_out (a delta-1 sub-index has starts of its own)");
+    if (nsel && d1 && d_ufirst && !d_unit_last)
+        return fail(TPF_EINVAL, "tpf_lists_extract: null d_unit_last (a delta-1 unit range starts from the skip table of tpf_lists_unit_last)");
+    if (ws_bytes < tpf_lists_extract_workspace_size(nsel))
+        return fail(TPF_EINVAL, "tpf_lists_extract: workspace too small");
+    hipStream_t s;
+    if (int rc = open_device_stream(stream, d_err, s))
+        return rc;
+    const tpf::ListsIndex X = lists_index(d_in, in_bytes, d_off, nunits, d_list_ptr, d_list_unit, nlists, d1, d_start0, d_unit_last);
+    return done(tpf::launch_lists_extract(X, d1 != 0, d_sel, d_ufirst, d_ucount, nsel, d_out, out_cap, d_off_out, units_cap, d_list_ptr_out,
+                                          d_list_unit_out, d1 ? d_start0_out : nullptr, d1 ? d_unit_last_out : nullptr, d_ws,
+                                          dev_err(d_err), s),
+                "tpf_lists_extract");
 }
 
 int tpf_copy_async(void * dst, const void * src, uint64_t bytes, void * stream)

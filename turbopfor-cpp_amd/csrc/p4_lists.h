@@ -280,6 +280,18 @@ hipError_t launch_lists_remove(const ListsIndex & X, bool d1, const uint32_t * p
                                const uint32_t * qlist, uint64_t nq, uint64_t stage_values, uint8_t * out, uint64_t out_cap,
                                uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out, uint32_t * lunit_out, uint32_t * ulast_out,
                                void * ws, unsigned long long * err, hipStream_t s);
+// a sub-index of a resident index, moved as bytes (p4_lists_extract.hip;
+// DESIGN.md 4.22).  Passes: plan over the SELECTION (the checks, the units,
+// values and bytes of every selected unit range) -> three run scans -> heads
+// (the verdict, both directories, the delta-1 starts, every selection's first
+// output byte, the capacity) -> offsets (d_off_out, d_unit_last_out) -> move
+// (stitch_tile, p4_lists_stitch.h, with no new bytes).  The workspace and the
+// plan are sized by nsel alone, the offsets by units_cap, the move by out_cap.
+size_t lists_extract_workspace(uint64_t nsel);
+hipError_t launch_lists_extract(const ListsIndex & X, bool d1, const uint32_t * sel, const uint32_t * ufirst, const uint32_t * ucount,
+                                uint64_t nsel, uint8_t * out, uint64_t out_cap, uint64_t * off_out, uint64_t units_cap, uint64_t * lptr_out,
+                                uint32_t * lunit_out, uint32_t * start0_out, uint32_t * ulast_out, void * ws, unsigned long long * err,
+                                hipStream_t s);
 // the unit offsets of a stream that has none, from the lists' byte spans and
 // the units' headers (p4_lists_scan.hip).  Passes: plan (one
 // thread per list: the checks, its unit count) -> run scan -> short (the

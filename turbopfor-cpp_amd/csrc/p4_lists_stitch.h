@@ -79,41 +79,38 @@ __device__ __forceinline__ void wave_move(uint8_t * dst, const uint8_t * src, ui
         dst[tail0 + (t - head)] = src[tail0 + (t - head)];
 }
 
-// A wave's tile of the output, n lists.  Args (AppArgs, RemArgs) names the old
-// index ix and, per list j of the result: lstart[j] (n + 1) its first output
-// byte, kbpre[j] (n + 1) the kept bytes of the lists before it, its kept bytes
-// at ix.in + ix.off[ix.list_unit[j]], its new bytes at sbytes +
-// noff[subase[j]]; hdr->go and hdr->fit gate the pass.
-template <class Args>
-__device__ __forceinline__ void stitch_tile(const Args & A, uint64_t nlists_out)
+// A wave's tile of the output, n lists: lstart[j] (n + 1) is list j's first
+// output byte; hdr->go and hdr->fit gate the pass.  Every list of the result is
+// a run of kept bytes followed by a run of new ones, and `src` says where they
+// come from: src(j, len, kb, ksrc, nsrc) is handed list j and its len output
+// bytes and sets kb, its kept bytes, ksrc, their address, and nsrc, the address
+// of the new bytes behind them.  NEW = false: no list has new bytes (kb = len)
+// and nsrc is not read (tpf_lists_extract, p4_lists_extract.hip).
+template <bool NEW, class Hdr, class Src>
+__device__ __forceinline__ void stitch_tile(const Hdr * hdr, const uint64_t * lstart, uint64_t nlists_out, uint8_t * out, const Src & src)
 {
-    if (A.hdr->go == 0u || A.hdr->fit == 0u)
+    if (hdr->go == 0u || hdr->fit == 0u)
         return;
     const uint32_t t = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t n = static_cast<uint32_t>(nlists_out);
-    const uint64_t total = A.lstart[n];
+    const uint64_t total = lstart[n];
     const uint64_t x0 = (static_cast<uint64_t>(blockIdx.x) * 4u + wv) * kListsAppendTile;
     if (x0 >= total)
         return;
     const uint64_t x1 = min_u64(x0 + kListsAppendTile, total);
-    uint32_t jb = find_list(A.lstart, n, x0, t);
+    uint32_t jb = find_list(lstart, n, x0, t);
     for (;;)
     {
         // lane t: list jb + t, its bytes [s, e) of the output
         const uint32_t j = jb + t;
         const bool in = j < n;
-        const uint64_t s = in ? A.lstart[j] : total;
-        const uint64_t e = in ? A.lstart[j + 1u] : total;
+        const uint64_t s = in ? lstart[j] : total;
+        const uint64_t e = in ? lstart[j + 1u] : total;
         const bool act = in && s < x1 && e > x0 && e > s;
         uint64_t kb = 0ull, ksrc = 0ull, nsrc = 0ull;
         if (act)
-        {
-            kb = A.kbpre[j + 1u] - A.kbpre[j];
-            if (kb != 0ull)
-                ksrc = reinterpret_cast<uint64_t>(A.ix.in) + A.ix.off[A.ix.list_unit[j]];
-            nsrc = reinterpret_cast<uint64_t>(A.sbytes) + A.noff[A.subase[j]];
-        }
+            src(j, e - s, kb, ksrc, nsrc);
         // a list of at most kAppLaneBytes bytes inside the tile is moved by its own lane, 64 lists at a time: a tile of
         // thousands of one-value lists would otherwise pay one memory round trip per list
         const uint64_t c0 = s > x0 ? s : x0, c1 = min_u64(e, x1);
@@ -127,11 +124,11 @@ __device__ __forceinline__ void stitch_tile(const Args & A, uint64_t nlists_out)
                 uint8_t v[8];
 #pragma unroll
                 for (uint32_t q = 0; q < 8u; ++q)
-                    v[q] = b0 + q < c1 ? *reinterpret_cast<const uint8_t *>((b0 + q < lk ? kp : np) + b0 + q) : uint8_t(0);
+                    v[q] = b0 + q < c1 ? *reinterpret_cast<const uint8_t *>((!NEW || b0 + q < lk ? kp : np) + b0 + q) : uint8_t(0);
 #pragma unroll
                 for (uint32_t q = 0; q < 8u; ++q)
                     if (b0 + q < c1)
-                        A.out[b0 + q] = v[q];
+                        out[b0 + q] = v[q];
             }
         }
         uint64_t mask = __ballot(act && !small);
@@ -144,19 +141,32 @@ __device__ __forceinline__ void stitch_tile(const Args & A, uint64_t nlists_out)
             // the kept bytes, clipped to the tile
             uint64_t w0 = ls > x0 ? ls : x0, w1 = min_u64(lk, x1);
             if (w0 < w1)
-                wave_move(A.out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(ksrc, l)) + (w0 - ls), static_cast<uint32_t>(w1 - w0),
-                          t);
+                wave_move(out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(ksrc, l)) + (w0 - ls), static_cast<uint32_t>(w1 - w0), t);
             w0 = lk > x0 ? lk : x0, w1 = min_u64(le, x1);
-            if (w0 < w1)
-                wave_move(A.out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(nsrc, l)) + (w0 - lk), static_cast<uint32_t>(w1 - w0),
-                          t);
+            if (NEW && w0 < w1)
+                wave_move(out + w0, reinterpret_cast<const uint8_t *>(readlane_u64(nsrc, l)) + (w0 - lk), static_cast<uint32_t>(w1 - w0), t);
         }
         // the batch's end: past the tile, or the last list
-        const uint64_t be = jb + 64u <= n ? A.lstart[jb + 64u] : total;
+        const uint64_t be = jb + 64u <= n ? lstart[jb + 64u] : total;
         if (jb + 64u >= n || be >= x1)
             break;
         jb += 64u;
     }
+}
+
+// The append's and the remove's lists: Args (AppArgs, RemArgs) names the old
+// index ix and, per list j of the result, kbpre[j] (n + 1) the kept bytes of
+// the lists before it, its kept bytes at ix.in + ix.off[ix.list_unit[j]], its
+// new bytes at sbytes + noff[subase[j]].
+template <class Args>
+__device__ __forceinline__ void stitch_tile(const Args & A, uint64_t nlists_out)
+{
+    stitch_tile<true>(A.hdr, A.lstart, nlists_out, A.out, [&A](uint32_t j, uint64_t, uint64_t & kb, uint64_t & ksrc, uint64_t & nsrc) {
+        kb = A.kbpre[j + 1u] - A.kbpre[j];
+        if (kb != 0ull)
+            ksrc = reinterpret_cast<uint64_t>(A.ix.in) + A.ix.off[A.ix.list_unit[j]];
+        nsrc = reinterpret_cast<uint64_t>(A.sbytes) + A.noff[A.subase[j]];
+    });
 }
 
 } // namespace tpf::dev

@@ -21,6 +21,14 @@ def shard_range(nblocks, world, rank):
     return lo, hi
 
 
+def term_shard(nlists, world, rank, device=None):
+    """The lists of `rank` when a lists index is sharded by term: the int32
+    `sel` tensor of the lists j with j % world == rank, ascending.  It feeds
+    turbopfor_amd.lists_extract, whose result is the rank's index; list k of
+    the shard is list rank + k * world of the whole."""
+    return torch.arange(rank, max(nlists, rank), world, dtype=torch.int32, device=device)
+
+
 def rebase(offsets, lo, hi):
     """Offsets of blocks [lo, hi) rebased to the shard's first byte, and the
     shard's byte range in the full stream."""

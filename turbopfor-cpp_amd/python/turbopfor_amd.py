@@ -1100,3 +1100,69 @@ def lists_remove(packed, offsets, list_ptr, list_unit, pos, pos_ptr, qlist, stag
                               _ptr(start0), _ptr(unit_last), _ptr(pos), npos, _ptr(pos_ptr), _ptr(qlist), nq, stage_values, *res_args,
                               _ptr(ws), ws.numel(), _ptr(err), stream if stream is not None else _stream(torch)))
     return res
+
+
+# ---- a sub-index of a resident index (include/turbopfor_gpu.h tpf_lists_extract) ----
+def lists_extract(packed, offsets, list_ptr, list_unit, sel, ufirst=None, ucount=None, d1=False, start0=None, unit_last=None, out=None,
+                  out_offsets=None, units_cap=None, err=None, ws=None, stream=None):
+    """A sub-index of a resident index, moved as bytes: list k of the result
+    is units [ufirst[k], ufirst[k] + ucount[k]) of list sel[k] (all of it with
+    ufirst=None), in the order given; repeats get a copy each.  packed /
+    offsets / list_ptr / list_unit / start0 / unit_last: the index as
+    decn256v32_lists_units reads it (unit_last required with d1 and ufirst,
+    optional otherwise); sel / ufirst / ucount: int32 CUDA tensors [nsel], the
+    arguments of decn256v32_lists_units -- qlist and the results of
+    lists_range_units feed the call unchanged.  Nothing is decoded: for an
+    index this library encoded the result is byte for byte encn256v32_lists of
+    the selected values with start0_out.  The frequency stream stored in
+    parallel is extracted by the same selection with d1=False.  out: uint8
+    CUDA tensor whose numel() is the byte capacity; out_offsets: int64 CUDA
+    tensor [units_cap + 1] (default units_cap: out_offsets.numel() - 1).  With
+    repeats the result can outgrow the index, so no capacity follows from the
+    sizes: when units_cap (or out_offsets) or out is not given, the selection's
+    unit and byte totals are summed on the device and read back, which costs a
+    device-to-host read -- the only synchronous path; pass out and out_offsets
+    (or units_cap) to stay asynchronous, and size them with a call on an empty
+    out (err = nunits + nsel + 1 and out_offsets[list_unit_out[-1]] bytes to
+    allocate).  err: optional int64 CUDA tensor [1] (-1 = clean).  stream: a
+    raw HIP stream handle (default: torch's current stream).  Returns (out,
+    out_offsets, list_ptr_out, list_unit_out, start0_out or None,
+    unit_last_out or None); unit_last_out is None without d1 or unit_last."""
+    import torch
+
+    if d1 and ufirst is not None and unit_last is None:
+        raise ValueError("lists_extract: d1=True with unit ranges needs unit_last (lists_unit_last)")
+    dev = sel.device
+    nlists = list_ptr.numel() - 1
+    nunits = offsets.numel() - 1 if offsets is not None and nlists > 0 else 0
+    nsel = sel.numel()
+    if units_cap is None and out_offsets is not None:
+        units_cap = out_offsets.numel() - 1
+    if units_cap is None or out is None:
+        nu = nb = 0
+        if nsel and nlists > 0 and nunits > 0:
+            # the totals of the selections the call will accept; it refuses the others itself
+            idx = sel.long() & 0xFFFFFFFF
+            ok = idx < nlists
+            idx = idx.clamp(max=nlists - 1)
+            lu0, lu1 = list_unit[idx].long() & 0xFFFFFFFF, list_unit[idx + 1].long() & 0xFFFFFFFF
+            units = (lu1 - lu0).clamp(min=0)
+            uf = ufirst.long() & 0xFFFFFFFF if ufirst is not None else torch.zeros_like(units)
+            uc = ucount.long() & 0xFFFFFFFF if ufirst is not None else units
+            ok = ok & (lu1 <= nunits) & (uf + uc <= units)
+            lo = (lu0 + uf).clamp(max=nunits)
+            hi = (lo + uc).clamp(max=nunits)
+            nu, nb = torch.stack([(uc * ok).sum(), ((offsets[hi] - offsets[lo]).clamp(min=0) * ok).sum()]).tolist()
+        if units_cap is None:
+            units_cap = int(nu)
+        if out is None:
+            out = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=dev)[:int(nb)]
+    res, res_args = _index_out(dev, nsel, bool(d1) and unit_last is not None, out, out_offsets, units_cap, None, None)
+    start0_out = torch.empty(max(nsel, 1), dtype=torch.int32, device=dev)[:nsel] if d1 else None
+    L = lib()
+    ws = _ws(ws, dev, L.tpf_lists_extract_workspace_size, nsel)
+    _check(L.tpf_lists_extract(_ptr(packed), packed.numel() if packed is not None else 0, _ptr(offsets), nunits, _ptr(list_ptr),
+                               _ptr(list_unit), nlists, int(bool(d1)), _ptr(start0), _ptr(unit_last), _ptr(sel), _ptr(ufirst), _ptr(ucount),
+                               nsel, *res_args[:6], _ptr(start0_out), res_args[6], _ptr(ws), ws.numel(), _ptr(err),
+                               stream if stream is not None else _stream(torch)))
+    return res[:4] + (start0_out, res[4])
